@@ -6,7 +6,8 @@ synthetic batches of the BASELINE.json configurations, one process per GPU.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times `--steps` steps and
+prints the headline; `--full` adds, after the timed region, these extra objects:
   roofline       the fused reconstruction-NLL kernel (HBM-bound): algorithmic bytes / device-clock duration,
   roofline_mfma  the register-stationary convolution kernels (MFMA-bound) and the whole step's GEMM FLOP rate,
   roofline_image the 3-channel image-layer kernels (HBM-bound),
@@ -14,7 +15,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
 Kernel durations come from the library's device-timestamp profiler (mvk_prof_enable: first workgroup in to last
 workgroup out on the constant-rate clock, the quantity a kernel trace reports) in eager steps of the same workload
 right after the graph-replayed timed region; a HIP-event bracket of the same launch is reported beside it.
-Nothing here reads /root/reference.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -362,6 +363,36 @@ def summarise(recs, kinds, boundary_s=0.0):
                 busy_avg_us=1e6 * busy / n)
 
 
+DUMP_PARAM_MAX = 12 << 20  # parameters written in full up to 48 MB; above that a fixed, seeded sample of this many
+
+
+def dump_outputs(path, out, model):
+    """What a caller of the timed step holds after its last step, as `path`/<name>.npy (float32, float64 kept): every tensor of
+    the step's ModelOutput (`loss`, `loss_sum`, `metrics.<key>`) and the updated parameters, flattened and concatenated in
+    `model.parameters()` order (`parameters`).  A model above DUMP_PARAM_MAX elements (cfg4, cfg5) is written as the elements
+    at DUMP_PARAM_MAX sorted indices drawn by a generator seeded with 0: the same elements from run to run.  Total < 64 MB."""
+    import numpy as np
+
+    def host(t):
+        t = t.detach()
+        return (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = host(v)
+        elif isinstance(v, dict):
+            arrays.update({f"{k}.{m}": host(t) for m, t in v.items() if torch.is_tensor(t)})
+    params = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).cpu()
+    if params.numel() > DUMP_PARAM_MAX:
+        idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_PARAM_MAX].sort().values
+        params = params[idx]
+    arrays["parameters"] = host(params)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: re-execute this command line under torch.distributed.run with N ranks on
     this node (rendezvous on 127.0.0.1, a free port) and return its exit status.  Rank 0 of the child job prints the line."""
@@ -404,6 +435,11 @@ def main():
                          "drain).  Built for VERDICT r5 item 1 and measured SLOWER on one MI355X (profiles/NOTES_r06.md section 2): opt-in")
     ap.add_argument("--no-rotate", action="store_true", help=argparse.SUPPRESS)  # (the default; kept for the round's A/B scripts)
     ap.add_argument("--cpu-budget", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region: per-kernel device timestamps, the roofline objects, the measured copy / MFMA "
+                         "ceilings and (one rank) the CPU baseline; a plain run prints the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss tensors and the updated parameters of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     # One process per GPU, launched from env as the reference's trainer expects (trainers/base/base_trainer_config.py:80-100,
@@ -516,28 +552,12 @@ def main():
         out = step()
     torch.cuda.synchronize()
     # Settling: the clock ramp of a freshly started process belongs outside the timed region by
-    # construction, not by the choice of --warmup.  Untimed groups of SETTLE_GROUP steps (device time of a group between two
-    # events) follow the W warm-up steps until two consecutive groups agree within 3 %, at most SETTLE_MAX groups; every rank
-    # runs the same number (the ranks agree on "settled" through an all-reduce), and the count goes into the line.
-    SETTLE_GROUP, SETTLE_MAX = 5, 10
-    settle_groups, prev_ms = 0, None
-    while settle_groups < SETTLE_MAX:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(SETTLE_GROUP):
-            out = step()
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / SETTLE_GROUP
-        settle_groups += 1
-        settled = prev_ms is not None and abs(ms - prev_ms) <= 0.03 * min(ms, prev_ms)
-        if use_dist:
-            flag = torch.tensor([1 if settled else 0], dtype=torch.int32, device=device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            settled = bool(int(flag.item()))
-        prev_ms = ms
-        if settled:
-            break
+    # construction, not by the choice of --warmup.  SETTLE_STEPS untimed steps follow the W warm-up steps on every rank: the
+    # most the earlier adaptive rule (groups of 5 until two agree within 3 %) ever ran, as a fixed count so that the state
+    # the timed region starts from, and with it what --dump-outputs writes, is the same from run to run.
+    SETTLE_STEPS = 50
+    for _ in range(SETTLE_STEPS):
+        out = step()
     if graphed is not None:
         graphed.drain()
     torch.cuda.synchronize()
@@ -563,9 +583,11 @@ def main():
     loss = float(out.loss.detach())
     if loss != loss:
         raise ArithmeticError("NaN detected in train loss")
+    if args.dump_outputs and rank == 0:  # before anything else steps the model
+        dump_outputs(args.dump_outputs, out, model)
 
     recs, events, step_flops, ms_instr, boundary = [], [], 0.0, None, 0.0
-    if rank == 0:
+    if rank == 0 and args.full:
         # Kernel durations: the same step again with the library's device-timestamp records switched on (captured into a
         # second graph: every replay accumulates into the records), `steps` replays right after the timed region.  The
         # stamps and the one-wave fold kernels behind the instrumented launches cost ~2 % of the step, which is why the
@@ -631,7 +653,7 @@ def main():
             "n_gpus": n_ranks,
             "steps": args.steps,
             "warmup": args.warmup,
-            "settle_steps": settle_groups * SETTLE_GROUP,  # untimed, behind the warm-up: groups of 5 until two agree within 3 % (<= 50)
+            "settle_steps": SETTLE_STEPS,  # untimed, behind the warm-up
             "ms_per_step": round(ms, 4),
             "ms_per_step_median": round(per_step_ms[len(per_step_ms) // 2], 4),
             "ms_per_step_min_max": [round(per_step_ms[0], 4), round(per_step_ms[-1], 4)],
@@ -666,6 +688,7 @@ def main():
                                           if kernels.DENSE16 else "")
                                        + "; tiled engine: 6 bf16 MFMAs on three pieces; latency-sized layers: exact fp32 FMA / MFMA"},
         }
+        # the objects below come from the records of the --full section (`recs` is empty without it)
         nll_generic = summarise(recs, {"recon_nll"}, boundary)
         imgf = summarise(recs, {"image_layer_fwd"}, boundary)
         # With the fused decoder tail (round 3) the large modality's reconstruction NLL lives in the epilogue of its decoder's last
@@ -795,14 +818,15 @@ def main():
                                  "achieved": round(d16b["work"] / d16b["seconds"] / 1e12, 1), "peak": round(MFMA_BF16_TFLOPS / 3, 1),
                                  "frac": round(d16b["work"] / d16b["seconds"] / 1e12 / (MFMA_BF16_TFLOPS / 3), 4),
                                  "us_per_step": round(1e6 * d16b["seconds"] / args.steps, 1)}
-        res["roofline_mfma"] = mf
+        if args.full:
+            res["roofline_mfma"] = mf
         img = {k: summarise(recs, {k}, boundary) for k in ("image_layer_fwd", "image_layer_bwd")}
         if any(img.values()):
             res["roofline_image"] = {k: {"bound": "hbm", "achieved": round(v["work"] / v["seconds"] / 1e9, 1),
                                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                          "frac": round(v["work"] / v["seconds"] / 1e9 / HBM_PEAK_GBS, 4),
                                          "avg_launch_us": round(v["avg_us"], 2)} for k, v in img.items() if v}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(w, args.cpu_budget)
         result_line = json.dumps(res)
     else:

@@ -833,6 +833,41 @@ def test_rccl_path_on_one_gpu_matches_the_plain_step(tmp_path):
     assert outs[1]["n_gpus"] == 1
 
 
+def test_bench_plain_run_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline only (no --full objects), `--steps` is the number of timed steps
+    `value` and `ms_per_step` come from, and `--dump-outputs` writes the last timed step's loss tensors and updated parameters
+    as float .npy files — bit-identical from run to run (fixed inputs, fixed number of untimed steps, deterministic step)."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MVK_FORCE_DIST"):
+        env.pop(k, None)
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "64",
+               "--dump-outputs", str(out_dir)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))})
+    d = lines[0]
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["unit"] == "samples/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(64 * 1e3 / d["ms_per_step"], rel=1e-3)
+    assert not {"roofline", "roofline_mfma", "roofline_image", "cpu_baseline"} & set(d)
+    a, b = dumps
+    assert {"loss", "loss_sum", "parameters"} <= set(a) and set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["parameters"].shape == (1552163,)  # MoPoE MnistSvhn, latent 20: every parameter
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert float(a["loss"]) == pytest.approx(d["config"]["final_loss"], abs=1e-4)
+
+
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_on_one_gpu():
     """The driver's multi-GPU launch line (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) with N = 2
@@ -847,7 +882,8 @@ def test_bench_two_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "64"]
+           "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "64",
+           "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
