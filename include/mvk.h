@@ -821,6 +821,30 @@ int mvk_dense16_unsplit(const void* hi, const void* lo, const float* bound, cons
 void mvk_dense16_debug(int flags); /* ablation switches of tools/dense16_probe.py (0 = the shipped kernels) */
 void mvk_dense16_debug_stamps(float* four_floats); /* flag 16: where the forward kernel's cycle stamps go (NULL: nowhere) */
 
+/* Nexus (models/nexus; nexus_model.py:209-254): the mean of the M <= MVK_MAX_MODALITIES message tensors msgs[m] [B, D] (HOST
+ * array of device pointers) over the kept modalities of each row -> agg [B, D] (0 for a row with nothing kept) and keep_out [B, M]
+ * (1 kept, 0 dropped or missing).  The keep set is, in this order of precedence: keep_in [B, M] (nonzero = kept), masks (HOST array
+ * of M [B] availability vectors), or forced perceptual dropout drawn from u [B, M + 1] uniforms on [0, 1) (mvk_device_rng): the row is
+ * dropped when u[b,0] < dropout_rate, then keeps 1 + floor(u[b,1] (M - 1)) modalities, the first ones of a partial Fisher-Yates
+ * shuffle driven by u[b,2..]; all three NULL keeps everything.  bwd: dmsgs[m] [B, D] (HOST array, overwritten) =
+ * keep[b,m] / count[b] * g[b]. */
+int mvk_nexus_aggregate_fwd(const float* const* msgs, const uint8_t* const* masks, const float* keep_in, const float* u,
+                            float dropout_rate, int M, int B, int D, float* agg, float* keep_out, void* stream);
+int mvk_nexus_aggregate_bwd(const float* keep, const float* g, int M, int B, int D, float* const* dmsgs, void* stream);
+
+/* Nexus top-level likelihood (nexus_model.py:153-168) for M modalities in one launch pair: rows[m][b] = gamma[m] mask_m[b]
+ * sum_d -ln N(z_m[b,d] | r_m[b,d], s_m), s_m^2 = s2[m] = mean over the whole [B, D_m] block of (z_m - r_m)^2 when adapt[m],
+ * else 1.  z, r, rows, masks (nullable), grows (entries nullable), dr: HOST arrays of device pointers; D, gamma, adapt: HOST
+ * arrays.  q [M, B] (out: the row sums of (z - r)^2) and s2 [M] are kept for the backward pass; work: scratch of
+ * M * ((B + 3) / 4) floats.  bwd: dr[m] [B, D_m] (overwritten) = d sum_b grows[m][b] rows[m][b] / d r_m, the path through s_m
+ * included; z gets no gradient (it is detached).  Block sums are fixed-order two-stage reductions: deterministic. */
+int mvk_nexus_top_nll_fwd(const float* const* z, const float* const* r, const uint8_t* const* masks, const int* D,
+                          const float* gamma, const int* adapt, int M, int B, float* const* rows, float* q, float* s2,
+                          float* work, void* stream);
+int mvk_nexus_top_nll_bwd(const float* const* z, const float* const* r, const uint8_t* const* masks, const int* D,
+                          const float* gamma, const int* adapt, int M, int B, const float* const* grows, const float* q,
+                          const float* s2, float* work, float* const* dr, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

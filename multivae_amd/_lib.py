@@ -198,6 +198,10 @@ PROTOTYPES = {
     "mvk_dense16_bwd_data": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p],
     "mvk_dense16_wgrad": [_p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i64, _i, _i, _i, _p],
     "mvk_dense16_unsplit": [_p, _p, _p, _p, _f, _i, _i, _i, _p, _p],
+    "mvk_nexus_aggregate_fwd": [_p, _p, _p, _p, _f, _i, _i, _i, _p, _p, _p],
+    "mvk_nexus_aggregate_bwd": [_p, _p, _i, _i, _i, _p, _p],
+    "mvk_nexus_top_nll_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
+    "mvk_nexus_top_nll_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p],
 }
 
 _lib = None

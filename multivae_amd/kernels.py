@@ -2857,6 +2857,8 @@ class ReconLossFn(Function):
         ctx.extra_shapes = [e.shape for e in extras]
         ctx.extra_grad = extra_grad
         ctx.rows = rows  # keep alive: metrics / debugging
+        if spec.get("rows_out") is not None:  # the caller's list receives the (unmasked) reconstruction rows: metrics
+            spec["rows_out"].extend(rows)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)  # no zero-fill launch for the gradient of `out` (never used)
         return loss, out
@@ -2920,6 +2922,80 @@ class GaussSampleKLFn(Function):
         call("mvk_gauss_sample_kl_bwd", ptr(mu), ptr(lv), ptr(eps), ptr(dw), ptr(dkl), K, B, L, ptr(dmu), ptr(dlv),
              stream_ptr())
         return None, dmu, dlv
+
+
+class NexusAggregateFn(Function):
+    """msgs_m [B, D] -> (agg [B, D], keep [B, M]): the Nexus message mean over the kept modalities (mvk_nexus_aggregate_fwd/bwd,
+    nexus_model.py:209-254).  Keep set: masks (list of M bool [B]), keep_in [B, M], or FPD from u [B, M + 1] uniforms on [0, 1)
+    with drop probability p; keep is the set used (non-differentiable)."""
+
+    @staticmethod
+    def forward(ctx, masks, keep_in, u, p, *msgs):
+        msgs = [_c(t) for t in msgs]
+        M = len(msgs)
+        B, D = msgs[0].shape
+        agg = _new((B, D), msgs[0])
+        keep = _new((B, M), msgs[0])
+        marr = ptr_array(masks) if masks is not None else None
+        call("mvk_nexus_aggregate_fwd", ptr_array(msgs), marr, ptr(keep_in), ptr(u), float(p), M, B, D, ptr(agg), ptr(keep),
+             stream_ptr())
+        ctx.save_for_backward(keep)
+        ctx.mark_non_differentiable(keep)
+        ctx.shape = (M, B, D)
+        return agg, keep
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, gkeep):
+        (keep,) = ctx.saved_tensors
+        M, B, D = ctx.shape
+        g = _c(g)
+        d = [torch.empty((B, D), dtype=torch.float32, device=g.device) for _ in range(M)]
+        call("mvk_nexus_aggregate_bwd", ptr(keep), ptr(g), M, B, D, ptr_array(d), stream_ptr())
+        return (None, None, None, None, *d)
+
+
+class NexusTopNLLFn(Function):
+    """(z_m [B, D_m] detached, r_m [B, D_m])_m -> rows [M, B]: gamma_m mask_m sum_d -ln N(z_m | r_m, s_m), s_m = 1 or the adapted
+    scale sqrt(mean((z_m - r_m)^2)) (mvk_nexus_top_nll_fwd/bwd, nexus_model.py:153-168).  Also returns s2 [M] (detached)."""
+
+    @staticmethod
+    def forward(ctx, masks, gammas, adapt, *zr):
+        M = len(zr) // 2
+        zs = [_c(t) for t in zr[:M]]
+        rs = [_c(t) for t in zr[M:]]
+        B = zs[0].shape[0]
+        ref = zs[0]
+        rows = _new((M, B), ref)
+        q = _new((M, B), ref)
+        s2 = _new((M,), ref)
+        work = _new((M * ((B + 3) // 4),), ref)
+        Ds = (C.c_int * M)(*[int(z.shape[1]) for z in zs])
+        gam = (C.c_float * M)(*[float(g) for g in gammas])
+        ad = (C.c_int * M)(*[1 if a else 0 for a in adapt])
+        marr = ptr_array(masks) if masks is not None else None
+        call("mvk_nexus_top_nll_fwd", ptr_array(zs), ptr_array(rs), marr, Ds, gam, ad, M, B, ptr_array(list(rows)), ptr(q),
+             ptr(s2), ptr(work), stream_ptr())
+        ctx.save_for_backward(*zs, *rs, q, s2)
+        ctx.masks, ctx.cfg, ctx.work = masks, (Ds, gam, ad, M, B), work
+        ctx.mark_non_differentiable(s2)
+        return rows, s2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grows, gs2):
+        Ds, gam, ad, M, B = ctx.cfg
+        saved = ctx.saved_tensors
+        zs, rs, q, s2 = saved[:M], saved[M:2 * M], saved[2 * M], saved[2 * M + 1]
+        if grows is None:
+            return (None, None, None) + (None,) * M + tuple(torch.zeros_like(r) for r in rs)
+        wait_loss(grows.device)  # the rows' gradient may come out of the loss assembly launch
+        grows = _c(grows)
+        dr = [torch.empty_like(r) for r in rs]
+        marr = ptr_array(ctx.masks) if ctx.masks is not None else None
+        call("mvk_nexus_top_nll_bwd", ptr_array(zs), ptr_array(rs), marr, Ds, gam, ad, M, B, ptr_array(list(grows)), ptr(q),
+             ptr(s2), ptr(ctx.work), ptr_array(dr), stream_ptr())
+        return (None, None, None) + (None,) * M + tuple(dr)
 
 
 class MVAEPosteriorFn(Function):
