@@ -230,7 +230,16 @@ int mvk_mmvae_std_bwd(const float* lv, const float* std, const float* dstd, int 
  *
  * MMVAE+ (mmvaePlus_model.py:122-262): the latent of a modality is [u (shared_dims), w (L - shared_dims)]; only the
  * first shared_dims dimensions enter the mixture (lq_all, lqz), the rest is scored by the conditioning modality's own
- * posterior: lqw[c][k,b] = sum_{l >= shared_dims} log q_c(z).  MMVAE: shared_dims = L, lqw = NULL. */
+ * posterior: lqw[c][k,b] = sum_{l >= shared_dims} log q_c(z).  MMVAE: shared_dims = L, lqw = NULL.
+ *
+ * Common to the three mvk_mmvae_latent_* / mvk_mmvae_objective_fwd entry points:
+ *   - 1 <= M <= MVK_MAX_MODALITIES, K >= 1, 1 <= shared_dims <= L, family NORMAL or LAPLACE_SOFTMAX;
+ *   - B == 0 is a no-op that returns MVK_OK: nothing is launched and no output is written, the loss scalar of
+ *     mvk_mmvae_objective_fwd included (the std and cross-latent entry points below treat rows == 0 the same way);
+ *     B < 0 is MVK_EINVAL;
+ *   - row indices are 32-bit: M * K * B must stay below 2^31 (MVK_EINVAL beyond); element offsets (times L) are 64-bit;
+ *   - the masks must leave at least one modality present in every row: a row with none divides by n_avail = 0 and
+ *     yields NaN, as the reference does. */
 int mvk_mmvae_latent_fwd(const float* const* mu, const float* const* std, const float* const* noise,
                          const uint8_t* const* masks, const float* prior_mean, const float* prior_std, int M,
                          int K, int B, int L, int family, float* const* z, float* const* lpz,
@@ -252,7 +261,8 @@ int mvk_mmvae_objective_fwd(const float* const* rows, const float* const* lpz, c
  * mvk_recon_nll_bwd with rowcoef = -w[c]/n_avail and the decoders' own backward).  Produces dmu[c], dstd[c]
  * [B,L] and dprior_std [B,L] (nullable): the per-row terms of d loss / d prior_std, which the caller sums over the rows
  * (mvk_colsum_acc: fixed order, bit-reproducible).  DReG: q parameters are detached inside log q and the total gradient
- * reaching z is scaled by w once more (the hook of mmvae_model.py:263-266). */
+ * reaching z is scaled by w once more (the hook of mmvae_model.py:263-266).  Rows b with mask_c[b] == 0 contribute nothing
+ * for conditioning modality c: dz_dec[c][:, b, :] is not read there (mvk_recon_nll_bwd leaves it zero, rowcoef being 0). */
 int mvk_mmvae_latent_bwd(const float* const* mu, const float* const* std, const float* const* noise,
                          const float* const* z, const uint8_t* const* masks, const float* prior_mean,
                          const float* prior_std, const float* const* w, const float* const* lq_all,

@@ -93,16 +93,24 @@ __global__ __launch_bounds__(256) void std_bwd_kernel(const float* __restrict__ 
     }
     return;
   }
-  // sd = softmax * L + 1e-6  ->  d lv_i = L * p_i * (dsd_i - sum_j dsd_j p_j)
-  const float invL = 1.0f / (float)L;
-  float dot = 0.f;
-  for (int l = lane; l < L; l += 64) dot += dsd[o + l] * (sd[o + l] - 1e-6f) * invL;
-  dot = wave_sum(dot);
+  // sd = softmax * L + 1e-6  ->  d lv_i = L * p_i * (dsd_i - sum_j dsd_j p_j).  p is recomputed from lv: recovering it as
+  // (sd - 1e-6) / L cancels for p L below ~1e-7 and loses the relative accuracy of those entries.
+  float mx = -INFINITY;
+  for (int l = lane; l < L; l += 64) mx = fmaxf(mx, lv[o + l]);
+  mx = wave_max(mx);
+  float s = 0.f, dot = 0.f;
   for (int l = lane; l < L; l += 64) {
-    const float p = (sd[o + l] - 1e-6f) * invL;
+    const float e = expf(lv[o + l] - mx);
+    s += e;
+    dot += dsd[o + l] * e;
+  }
+  s = wave_sum(s);
+  dot = wave_sum(dot) / s;
+  for (int l = lane; l < L; l += 64) {
+    const float p = expf(lv[o + l] - mx) / s;
     dlv[o + l] = (float)L * p * (dsd[o + l] - dot);
   }
-  (void)lv;
+  (void)sd;
 }
 
 // ---- forward: samples, prior log-density, mixture log-density --------------------------------------------------
@@ -237,7 +245,7 @@ __global__ __launch_bounds__(1024) void objective_kernel(const ObjPtrs p, int M,
     float obj = 0.f;
     for (int k = 0; k < K; ++k) {
       const long long o = (long long)k * B + b;
-      const float wk = expf(lw[o] - lse);
+      const float wk = expf(lw[o] - mx) / s;  // not expf(lw - lse): rounding lse (|lw| ~ 3e3) would scale the whole column
       w[o] = wk;
       rc[o] = -wk * mc / (float)navail;  // d loss / d lw[c][k,b]
       obj += wk * lw[o];
@@ -515,6 +523,7 @@ int mvk_mmvae_latent_fwd(const float* const* mu, const float* const* sd, const f
       K < 1 || L < 1 || family < 0 || family > 1 || shared_dims < 1 || shared_dims > L || (shared_dims < L && !lqw))
     return MVK_EINVAL;
   if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
+  if ((long long)M * K * B > 0x7fffffffLL) return MVK_EINVAL;  // row indices are int: M*K*B < 2^31 (include/mvk.h)
   MmPtrs p{};
   for (int m = 0; m < M; ++m) {
     if (!mu[m] || !sd[m] || !noise[m] || !z[m] || !lpz[m] || !lqz[m] || !lq_all[m]) return MVK_EINVAL;
@@ -539,7 +548,9 @@ int mvk_mmvae_objective_fwd(const float* const* rows, const float* const* lpz, c
                             const uint8_t* const* masks, int M, int K, int B, int dreg, float* const* lw_out,
                             float* const* w, float* const* rowcoef, float* loss, const float* const* lqw, float beta,
                             void* stream) {
-  if (!rows || !lpz || !lqz || !lw_out || !w || !rowcoef || !loss || M < 1 || M > MAXM || K < 1 || B < 1) return MVK_EINVAL;
+  if (!rows || !lpz || !lqz || !lw_out || !w || !rowcoef || !loss || M < 1 || M > MAXM || K < 1 || B < 0) return MVK_EINVAL;
+  if (B == 0) return MVK_OK;  // zero rows: nothing is launched, loss included (include/mvk.h)
+  if ((long long)M * K * B > 0x7fffffffLL) return MVK_EINVAL;  // row indices are int: M*K*B < 2^31 (include/mvk.h)
   ObjPtrs p{};
   for (int m = 0; m < M; ++m) {
     if (!lpz[m] || !lqz[m] || !lw_out[m] || !w[m] || !rowcoef[m]) return MVK_EINVAL;
@@ -570,6 +581,7 @@ int mvk_mmvae_latent_bwd(const float* const* mu, const float* const* sd, const f
       M < 1 || M > MAXM || K < 1 || L < 1 || family < 0 || family > 1 || shared_dims < 1 || shared_dims > L)
     return MVK_EINVAL;
   if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
+  if ((long long)M * K * B > 0x7fffffffLL) return MVK_EINVAL;  // row indices are int: M*K*B < 2^31 (include/mvk.h)
   BwdPtrs p{};
   for (int m = 0; m < M; ++m) {
     if (!mu[m] || !sd[m] || !noise[m] || !z[m] || !w[m] || !lq_all[m] || !lqz[m] || !dz_dec[m] || !dmu[m] || !dsd[m])
