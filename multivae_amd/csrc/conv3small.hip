@@ -7,8 +7,8 @@
 //   * smallcin:  Y[n,H,W,Cout] = act(conv(X[n,H,W,Cs<=4]) + b) (* act'(mask)): a workgroup takes a band of 8 image rows, the
 //     3-channel tile with halo sits in LDS (broadcast reads), a thread keeps W[:, 4 couts] in registers (27 float4) and
 //     writes 16 bytes per position.  Also the backward-data pass of the image-producing layer (same shape, flipped pack).
-//   * smallcout: Y[n,H,W,Cs<=4] = act(conv(X[n,H,W,Cin]) + b): the Cin-channel tile with halo and the weights in LDS, two
-//     threads per position split the taps and combine through a wave shuffle.
+//   * smallcout: Y[n,H,W,Cs<=4] = act(conv(X[n,H,W,Cin]) + b): a thread owns one output position and its Cs channels, the
+//     input tile with halo is staged in LDS 16 channels at a time, the weights are scalar operands.
 //   * wgrad:     dW[(tap, cs)][cb] = sum_pos S[pos + tap][cs] B[pos][cb] for either role of the small tensor; per-workgroup
 //     slabs, ordered (deferred) finish into the reference layout.
 #include <cstdlib>
@@ -95,77 +95,10 @@ __global__ __launch_bounds__(256) void conv3_smallcin_kernel(const C3Args g) {
 }
 
 
-// ---- many channels -> output image ----------------------------------------------------------------------------------------
-// Tile = 8 rows x 16 columns of output positions; the Cin-channel input tile with halo and the weights sit in LDS; a wave owns
-// two tile rows (16 positions each) as MFMA row tiles: D[pos][co] += X[pos + tap][c] W[(tap, c)][co] on
-// v_mfma_f32_16x16x4_f32 (exact fp32; only Cs <= 4 of the 16 columns are used — the layer is still bound by streaming X
-// once).  Within a 16-channel block the k index is permuted so that a lane reads its four channels with one 16-byte load.
-constexpr int C3_TR = 8, C3_TC = 16;
-
-template <int CS>
-__global__ __launch_bounds__(256) void conv3_smallcout_kernel(const C3Args g) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int Cin = g.Cin, H = g.H, W = g.W;
-  const int PS = Cin + 4;                        // floats per tile pixel (16-byte shifted rows)
-  const int TWp = (C3_TC + 2) * PS;              // floats per tile row
-  float* xt = sm;                                // [(TR + 2)][(TC + 2)][PS]
-  float* wt = sm + (C3_TR + 2) * TWp;            // [9 * Cin][4]  (columns >= CS zero)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
-  const int tcols = (W + C3_TC - 1) / C3_TC, trows = (H + C3_TR - 1) / C3_TR;
-  const int img = blockIdx.x / (tcols * trows), trem = blockIdx.x % (tcols * trows);
-  const int y0 = (trem / tcols) * C3_TR, x0 = (trem % tcols) * C3_TC;
-  for (int i = tid; i < 9 * Cin * 4; i += 256) {
-    const int k = i >> 2, co = i & 3;
-    wt[i] = co < CS ? g.Wp[(long long)k * CS + co] : 0.f;
-  }
-  const float* ximg = g.X + (long long)img * H * W * Cin;
-  const int c4n = Cin / 4;
-  for (int i = tid; i < (C3_TR + 2) * (C3_TC + 2) * c4n; i += 256) {
-    const int pix = i / c4n, q = i - pix * c4n;
-    const int r = pix / (C3_TC + 2), cx = pix - r * (C3_TC + 2);
-    const int yy = y0 + r - 1, xx = x0 + cx - 1;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = *reinterpret_cast<const f32x4*>(ximg + ((long long)yy * W + xx) * Cin + 4 * q);
-    *reinterpret_cast<f32x4*>(xt + r * TWp + cx * PS + 4 * q) = v;
-  }
-  __syncthreads();
-  const float bias = (g.bias && l15 < CS) ? g.bias[l15] : 0.f;
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt) {
-    const int r = wave * 2 + mt;  // tile row of this MFMA tile: positions (y0 + r, x0 + 0..15)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int tap = 0; tap < 9; ++tap) {
-      const int dy = tap / 3, dx = tap - dy * 3;
-      const float* arow = xt + (r + dy) * TWp + (l15 + dx) * PS + 4 * lq;  // A: position l15, channels cb*16 + 4 lq .. +3
-      const float* brow = wt + (tap * Cin + 4 * lq) * 4 + (l15 & 3);       // B: k = cb*16 + 4 lq + t, column l15 (& 3)
-      for (int cb = 0; cb < Cin; cb += 16) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(arow + cb);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t], brow[(cb + t) * 4], acc, 0, 0, 0);
-      }
-    }
-    // D[i = 4 lq + rr][j = l15]: position x0 + 4 lq + rr of row y0 + r, output channel l15
-    const int yy = y0 + r;
-    if (l15 < CS && yy < H) {
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int xx = x0 + 4 * lq + rr;
-        if (xx < W) {
-          const long long o = (((long long)img * H + yy) * W + xx) * CS + l15;
-          float v = mvk_act(acc[rr] + bias, g.act);
-          if (g.mask_src) v *= mvk_act_grad_from_out(g.mask_src[o], g.mask_act);
-          g.Y[o] = v;
-        }
-      }
-    }
-  }
-}
-
-
-// ---- many channels -> output image, on the vector ALU (end of round 3) ------------------------------------------------------
-// The MFMA version above uses 3 of the 16 columns of every v_mfma_f32_16x16x4_f32 and reads one B value from LDS per
-// instruction: 1101 us per launch at cfg4's decoder batch (1600 images of 28x28, 321 MB of input whose HBM time is 64 us), 164 us
-// at cfg5's.  Here a thread owns ONE output position and its CS <= 4 channels: 9 Cin CS FMAs in exact fp32, the input tile
+// ---- many channels -> output image, on the vector ALU ----------------------------------------------------------------------
+// (An MFMA kernel for this shape used 3 of the 16 columns of every v_mfma_f32_16x16x4_f32 and read one B value from LDS per
+// instruction: 1101 us per launch at cfg4's decoder batch — 1600 images of 28x28, 321 MB of input whose HBM time is 64 us —, 164 us
+// at cfg5's; removed.)  A thread owns ONE output position and its CS <= 4 channels: 9 Cin CS FMAs in exact fp32, the input tile
 // (8 x 32 positions + halo) staged 16 channels at a time as [pixel][16 + 4 pad floats] (80-byte stride: conflict-free 16-byte
 // reads), the chunk's weights [tap][co][16] read as LDS broadcasts.  27 KB of LDS and ~40 registers: 5 workgroups per CU hide
 // the staging of one behind the FMAs of the others.
@@ -355,35 +288,13 @@ int conv3_smallcout(const float* X, const float* Wp, const float* bias, float* Y
   static const int off = mvk_tune("MVK_CONV3SMALL") ? atoi(mvk_tune("MVK_CONV3SMALL")) == 0 : 0;
   if (off || Cout < 1 || Cout > 4 || Cin % 16 != 0 || Cin < 16 || Cin > 256 || n < 1 || !mvk_aligned16(X)) return 1;
   C3Args a{X, Wp, bias, Y, mask_src, n, H, W, Cin, Cout, act, mask_act, nullptr};
-  static const int mfma = mvk_tune("MVK_SMALLCOUT_MFMA") ? atoi(mvk_tune("MVK_SMALLCOUT_MFMA")) : 0;  // A/B: the MFMA kernel
-  if (!mfma) {
-    const dim3 vgrid((unsigned)((long long)n * ((W + C3V_TC - 1) / C3V_TC) * ((H + C3V_TR - 1) / C3V_TR)));
-    switch (Cout) {
-      case 1: hipLaunchKernelGGL(conv3_smallcout_v_kernel<1>, vgrid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL(conv3_smallcout_v_kernel<2>, vgrid, dim3(256), 0, s, a); break;
-      case 3: hipLaunchKernelGGL(conv3_smallcout_v_kernel<3>, vgrid, dim3(256), 0, s, a); break;
-      default: hipLaunchKernelGGL(conv3_smallcout_v_kernel<4>, vgrid, dim3(256), 0, s, a); break;
-    }
-    MVK_CHECK_LAUNCH();
-    return MVK_OK;
-  }
-  const int tcols = (W + C3_TC - 1) / C3_TC, trows = (H + C3_TR - 1) / C3_TR;
-  const size_t lds = ((size_t)(C3_TR + 2) * (C3_TC + 2) * (Cin + 4) + (size_t)9 * Cin * 4) * sizeof(float);
-  const dim3 grid((unsigned)(n * tcols * trows));
-#define MVK_C3SC(CS_)                                                                                                   \
-  {                                                                                                                     \
-    if (lds > 64 * 1024)                                                                                                \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_smallcout_kernel<CS_>),                             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-    hipLaunchKernelGGL(conv3_smallcout_kernel<CS_>, grid, dim3(256), lds, s, a);                                        \
-  }
+  const dim3 vgrid((unsigned)((long long)n * ((W + C3V_TC - 1) / C3V_TC) * ((H + C3V_TR - 1) / C3V_TR)));
   switch (Cout) {
-    case 1: MVK_C3SC(1) break;
-    case 2: MVK_C3SC(2) break;
-    case 3: MVK_C3SC(3) break;
-    default: MVK_C3SC(4) break;
+    case 1: hipLaunchKernelGGL(conv3_smallcout_v_kernel<1>, vgrid, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(conv3_smallcout_v_kernel<2>, vgrid, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL(conv3_smallcout_v_kernel<3>, vgrid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL(conv3_smallcout_v_kernel<4>, vgrid, dim3(256), 0, s, a); break;
   }
-#undef MVK_C3SC
   MVK_CHECK_LAUNCH();
   return MVK_OK;
 }

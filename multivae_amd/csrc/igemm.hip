@@ -61,8 +61,7 @@ static int defer_push(const Epilogue& e, int M, int N, int nz, long long zstride
   it.nz = nz;
   it.zstride = zstride;
   it.vec4 = ((long long)M * N) % 4 == 0 && zstride % 4 == 0 && mvk_aligned16(e.ws);
-  static const int zl_env = mvk_tune("MVK_DEFER_ZL") ? atoi(mvk_tune("MVK_DEFER_ZL")) : 5;  // z-lanes of long reductions (A/B)
-  it.zl_bits = nz > 64 ? zl_env : 3;
+  it.zl_bits = nz > 64 ? 5 : 3;  // z-lanes of long reductions
   g_defer.items.push_back(it);
   return MVK_OK;
 }
@@ -126,12 +125,7 @@ static int defer_flush_locked(hipStream_t s, bool last) {
       const int per = (256 >> it.zl_bits) * (it.vec4 ? 4 : 1);
       blocks += (unsigned)(((long long)it.M * it.N + per - 1) / per);
     }
-    // MVK_DEFER_FLUSH_GRID=n: a PARTIAL flush (it runs beside the step's chain) on at most n workgroups (A/B; 0 = one per index)
-    static const int part_grid = mvk_tune("MVK_DEFER_FLUSH_GRID") ? atoi(mvk_tune("MVK_DEFER_FLUSH_GRID")) : 0;
-    if (!last && part_grid > 0 && blocks > (unsigned)part_grid)
-      hipLaunchKernelGGL(splitk_reduce_batch_loop_kernel, dim3(part_grid), dim3(256), 0, s, T, blocks);
-    else
-      hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(blocks), dim3(256), 0, s, T);
+    hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(blocks), dim3(256), 0, s, T);
     if (hipGetLastError() != hipSuccess) rc = MVK_ELAUNCH;
   }
   g_defer.items.clear();
@@ -839,11 +833,6 @@ int mvk_linear_bwd_data(const float* dY, const float* W, float* dX, int M, int N
   d.N = K;
   d.K = N;
   hipStream_t s = mvk_stream(stream);
-  static const int smallk_bwd = mvk_tune("MVK_SMALLK_BWD") ? atoi(mvk_tune("MVK_SMALLK_BWD")) : 0;  // measured +10 us per step on the heads' backward-data: off
-  if (smallk_bwd && N <= 32 && !y_out && !colsum_acc) {  // backward-data out of a narrow layer (the encoder heads)
-    const int rc = smallk_fwd(dY, W, K, 1, nullptr, 1, MVK_ACT_NONE, dX, M, K, N, s, prev_out, prev_act, accumulate);
-    if (rc != 1) return rc;
-  }
   if (!colsum_acc) return launch_auto(d, ws, ws_floats, s);
   // bias gradient of the previous layer = column sums of dX: fused into the epilogue unless the launch splits K
   const long long tiles = (long long)((d.M + 127) / 128) * ((d.N + 63) / 64);
@@ -924,8 +913,8 @@ int mvk_gemm(const float* A, const float* B, float* C, int M, int N, int K, int 
              int bias_mod, int act, int accumulate, const float* a_act_src, int a_act, const float* c_act_src,
              int c_act, float* ws, int64_t ws_floats, void* stream) {
   if (!A || !B || !C || M < 0 || N <= 0 || K <= 0) return MVK_EINVAL;
-  static const int smallk_bwd = mvk_tune("MVK_SMALLK_BWD") ? atoi(mvk_tune("MVK_SMALLK_BWD")) : 0;  // measured +10 us per step on the heads' backward-data: off
-  if (K <= 32 && !ta && !a_act_src && M > 0 && (smallk_bwd || (!accumulate && !c_act_src))) {
+  // (the narrow kernel for the heads' backward-data too — accumulate / c_act_src — measured +10 us per step: the tiled engine)
+  if (K <= 32 && !ta && !a_act_src && M > 0 && !accumulate && !c_act_src) {
     const int rc = smallk_fwd(A, B, tb ? 1 : N, tb ? K : 1, bias, bias_mod, act, C, M, N, K, mvk_stream(stream), c_act_src,
                               c_act, accumulate);
     if (rc != 1) return rc;

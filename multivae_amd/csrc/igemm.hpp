@@ -971,9 +971,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_batch_kernel(const DeferTab
     splitk_reduce_bodyv<1>(E, it.M, it.N, it.nz, it.zstride, blockIdx.x - it.blk0, it.zl_bits, red);
 }
 
-// The same launch with a bounded grid (a workgroup walks the table's workgroup indices grid by grid): for a PARTIAL flush that
-// runs beside the step's last dependent chain — 11 k short workgroups take every free CU slot from the launches it runs beside,
-// a few hundred long ones leave room (mvk_defer_flush; the final flush stays wide: it IS the chain).
+// The same launch with a bounded grid (a workgroup walks the table's workgroup indices grid by grid).  NOT LAUNCHED any more: as
+// the partial flush beside the step's last chain it lost at every grid size (profiles/NOTES_r06.md section 10) and its switch is
+// gone.  The definition stays for one reason: without it the compiler allocates registers differently in
+// splitk_reduce_batch_kernel above (same source, 24 changed instructions), and that kernel is on every step's path — deleting
+// this one belongs to a change that re-measures the other.
 __global__ __launch_bounds__(256) void splitk_reduce_batch_loop_kernel(const DeferTable T, const unsigned total) {
   __shared__ float red[32 * 33];
   for (unsigned b = blockIdx.x; b < total; b += gridDim.x) {

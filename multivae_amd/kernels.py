@@ -74,10 +74,6 @@ def _ws(like):
 # gradient that accumulates into the flat buffer (split-K slabs, column-sum partials, convolution weight-gradient slabs)
 # are queued and run in ONE launch at exit instead of one small launch each in the middle of the backward chain.
 DEFER = _lib.tune("MVK_DEFER", "1") != "0"
-# MVK_DEFER_SIDE=1: flush the decoders' finishes on a side stream when the posterior backward starts.  Measured on the
-# headline step: 1.528 ms vs 1.50 ms with one flush at the end (the streaming finish kernel delays every launch of the
-# latency-bound encoder backward it runs beside): off.
-DEFER_SIDE = _lib.tune("MVK_DEFER_SIDE", "0") == "1"
 # The arena starts at 64 MB and grows between steps to what the last step asked for (mvk_defer_wanted), up to MVK_DEFER_MB
 # (default 1024): an MLP model keeps 64 MB, the MnistSvhn models settle at ~200 MB, the ResNet configurations at the cap
 # (a fixed 512 MB per device was wasteful for small models and too small for cfg5).  Grown only outside a stream
@@ -129,50 +125,19 @@ class late_leaves:
 
 
 _LATE_CALLS = {}  # device -> closures run on the late-leaf stream when deferred_reductions ends (behind every other late leaf)
-# MVK_LATE_DENSE=1: the MLP decoder's weight gradients are postponed behind the convolutional late leaves, into the tail of the
-# step.  MEASURED (three same-box pairs): 1.099 / 1.093 / 1.094 ms without vs 1.114 / 1.104 / 1.106 ms with — the tail (the
-# encoders' backward: a dependent chain of small kernels) slows down by what the decoder window gains; off.
-LATE_DENSE = _lib.tune("MVK_LATE_DENSE", "0") == "1"
+# Of the MLP decoder's weight gradients only the first layer's (a split-K launch of 16 us alone, 50-60 us beside the convolutions)
+# is postponed: autograd orders the posterior's backward behind EVERYTHING the decoder's backward node enqueued on its stream,
+# leaves included.  MEASURED (three same-box pairs): 1.046 / 1.050 / 1.039 -> 1.042 / 1.040 / 1.032 ms.  Postponing ALL of them
+# lost (1.099 / 1.093 / 1.094 ms without vs 1.114 / 1.104 / 1.106 ms with: the tail — the encoders' backward, a dependent chain of
+# small kernels — slows down by what the decoder window gains).
 
 
-# Only the first layer's weight gradient (a split-K launch of 16 us alone, 50-60 us beside the convolutions) is postponed: autograd
-# orders the posterior's backward behind EVERYTHING the decoder's backward node enqueued on its stream, leaves included.
-# MEASURED (three same-box pairs): 1.046 / 1.050 / 1.039 -> 1.042 / 1.040 / 1.032 ms.  MVK_LATE_DW0=0: inside the node.
-LATE_DW0 = _lib.tune("MVK_LATE_DW0", "1") != "0"
-# MVK_SKIP_LATE=1 (TIMING ONLY, wrong gradients): the SVHN decoder's late weight gradients are not launched at all — the bound of
-# what moving them out of the step's tail can gain (NOTES_r06 section 1)
-SKIP_LATE = _lib.tune("MVK_SKIP_LATE", "0") == "1"
-
-
-# MVK_LATE_GATE=1: the large decoder's register-stationary weight gradients (one 512-register wave per SIMD on every CU for ~150 us)
-# start only behind the convolutional encoder's LAST backward-data launch (late_gate): the encoder's own 512-register launches
-# cannot start on a CU that holds such a workgroup, its small-register ones (heads, split-K weight gradients) can run beside them
-LATE_GATE = _lib.tune("MVK_LATE_GATE", "0") == "1"
-_LATE_GATE_EV = {}  # device -> event recorded by late_gate (main stream)
-_LATE_GATED = {}    # device -> closures that wait for it
-
-
-def late_gate(device):
-    """SVHNEncoderFn.backward, behind its last backward-data launch (the caller's stream must be the step's main stream)."""
-    if LATE_GATE and device in _LATE_GATED:
-        _LATE_GATE_EV[device] = torch.cuda.current_stream(device).record_event()
-
-
-def run_gated(device, fn, *reads):
-    """Inside deferred_reductions: fn() on the late-leaf stream, enqueued at the end of the scope behind every other postponed
-    leaf and behind the late_gate event (when one was recorded).  False: the caller runs fn itself."""
-    if not (LATE_GATE and LATE_LEAVES) or device.type != "cuda" or device not in _DEFER_ACTIVE:
-        return False
-    _LATE_GATED.setdefault(device, []).append((fn, reads))
-    return True
-
-
-def run_last(device, fn, *reads, force=False, params=()):
+def run_last(device, fn, *reads, params=()):
     """Inside deferred_reductions: run fn() on the late-leaf stream AFTER everything else the backward pass puts there (the
     enqueue itself is postponed to the end of the scope), i.e. in the launch-latency-bound tail of the step where the chip is
     mostly idle, instead of beside the decoders' backward-data chains whose window is throughput-bound.  Returns False when
     there is no such scope (the caller runs fn itself)."""
-    if not (LATE_LEAVES and (LATE_DENSE or force)) or device.type != "cuda" or device not in _DEFER_ACTIVE:
+    if not LATE_LEAVES or device.type != "cuda" or device not in _DEFER_ACTIVE:
         return False
     _LATE_CALLS.setdefault(device, []).append((fn, reads))
     op = _OVERLAP.get(device)
@@ -236,11 +201,7 @@ class OverlapPoint:
 # fit beside anything: the kind of launch the head of the step has room for).
 ROT_SVHN = int(_lib.tune("MVK_ROT_SVHN", "1"))
 ROT_MLP = int(_lib.tune("MVK_ROT_MLP", "1"))
-# MVK_ROT_ARM=1: the head branch forks BEHIND the first launch of the forward pass (so that the main chain is the root chain that is
-# enqueued first); measured slower than forking in front of it (0.955 vs 0.948 ms, three pairs; unrotated 0.938): off
-ROT_ARM = _lib.tune("MVK_ROT_ARM", "0") != "0"
 _ROTATE = {}  # device -> Rotation, while trainers.graph enqueues / captures a rotated step
-_ROTATE_ARMED = {}  # device -> Rotation whose head branch starts behind the forward pass's first launch (Rotation.arm)
 
 
 def rotation(device):
@@ -293,23 +254,6 @@ class Rotation:
     def push(self, fn, params, prepare=None):
         self.leaves.append((fn, tuple(params), prepare))
 
-    def arm(self, update=None):
-        """Inside deferred_reductions, before the forward pass: begin_step(update) will run behind the FIRST launch of the
-        forward pass on the caller's stream (pack_scope's fill of the amax arena), not in front of it — in a captured graph the
-        root chain that is enqueued first gets the launching hardware queue, and that has to be the step's main chain (with the
-        head branch enqueued first the whole forward chain started ~20 us later: profiles/r06_rotated_small_step_timeline.txt)."""
-        self.armed = (update,)
-        _ROTATE_ARMED[self.device] = self
-
-    def begin_if_armed(self):
-        if self.armed is not None:
-            update, = self.armed
-            self.armed = None
-            _ROTATE_ARMED.pop(self.device, None)
-            self.begin_step(update)
-
-    armed = None
-
     def begin_step(self, update=None):
         """Inside deferred_reductions, at the head of the forward pass: the branch of the previous step's leaves.  update: the
         closure that applies the optimizer to the rotated parameters (captured passes only; eager warm-up passes leave the
@@ -350,7 +294,6 @@ class Rotation:
     def end_step(self):
         """Behind the backward pass: the branch is joined (it is, transitively, when a decoder waited for it), the leaves the
         backward pass registered become the next head's."""
-        self.begin_if_armed()  # (a forward pass without a pack_scope never started it)
         _ROTATE.pop(self.device, None)
         if self.open:
             self.wait()
@@ -450,13 +393,8 @@ class deferred_reductions:
     def __exit__(self, et, ev, tb):
         if self.on:
             dev = self.grad.device
-            late = list(_LATE_CALLS.pop(dev, ()))
-            gated = _LATE_GATED.pop(dev, ())
-            gate_ev = _LATE_GATE_EV.pop(dev, None)
-            if gated and gate_ev is None:
-                late += list(gated)  # nobody recorded the gate: ordinary postponed leaves
-                gated = ()
-            if late or gated:  # postponed leaves: enqueued now, on the late-leaf stream, behind the other late leaves
+            late = _LATE_CALLS.pop(dev, ())
+            if late:  # postponed leaves: enqueued now, on the late-leaf stream, behind the other late leaves
                 # Ordered behind a MAIN-stream event (late_ready: recorded where the posterior's backward starts, i.e. behind the
                 # join of every decoder's backward), never behind the producer's branch stream itself: the partial flush on a branch
                 # stream waits for the late-leaf stream, a late-leaf stream that waited for that branch stream made the two
@@ -472,19 +410,11 @@ class deferred_reductions:
                         for t in reads:
                             t.record_stream(st)
                         fn()
-                    if gated:
-                        st.wait_event(gate_ev)
-                        for fn, reads in gated:
-                            for t in reads:
-                                t.record_stream(st)
-                            fn()
             _DEFER_ACTIVE.discard(dev)
             _LATE_READY.pop(dev, None)
             _LOSS_EVENT.pop(dev, None)  # the late-leaf stream is joined below
             _LOSS_POSTPONED.pop(dev, None)
             _BIG_LATE.discard(dev)
-            _LATE_GATE_EV.pop(dev, None)
-            _LATE_GATED.pop(dev, None)
             cur = torch.cuda.current_stream(dev)
             for st in dict.fromkeys(_LATE_USED.pop(dev, ())):  # the late leaves (below) and sibling flushes end here
                 if st != cur:
@@ -502,27 +432,19 @@ class deferred_reductions:
         return False
 
 
-# MVK_FLUSH_SIBLING=1: when the LAST backward node of the step starts (the convolutional encoder: ~140 us of launch-latency-bound
+# When the LAST backward node of the step starts (the convolutional encoder: ~140 us of launch-latency-bound
 # chain on its own stream), everything queued so far is finished on the other branch stream, which is idle by then, instead of
 # in one launch behind the chain.
-FLUSH_SIBLING = _lib.tune("MVK_FLUSH_SIBLING", "1") != "0"
-# MVK_FLUSH_ON_LATE=1: that partial flush on the late-leaf stream, directly behind the large decoder's late weight gradients (A/B)
-FLUSH_ON_LATE = _lib.tune("MVK_FLUSH_ON_LATE", "0") == "1"
 _BRANCH_SET = {}  # device -> the streams of the last run_branches call (main first)
 
 
 def defer_flush_sibling(device, node_params=()):
     """node_params: the parameters of the backward node that calls this (the LAST one of the step): with an OverlapPoint open,
     everything else's gradient is final behind the flush, and the point is recorded there."""
-    if not (FLUSH_SIBLING and DEFER) or device.type != "cuda" or device not in _DEFER_ACTIVE:
+    if not DEFER or device.type != "cuda" or device not in _DEFER_ACTIVE:
         return
     cur = torch.cuda.current_stream(device)
     sib = next((st for st in _BRANCH_SET.get(device, ()) if st != cur), None)
-    if FLUSH_ON_LATE and device in _BIG_LATE and _OVERLAP.get(device) is None:
-        # the partial flush has to wait for the decoder's late weight gradients anyway (their slabs are most of what it adds): on
-        # THEIR stream it starts the moment they end — beside the encoders' backward-data launches — instead of behind the other
-        # encoder's whole backward chain on the sibling stream, where its 165 MB ran beside the last launches of the step's chain
-        sib = _side_stream(device, 30)
     if sib is None or _lib.load().mvk_defer_pending() == 0:
         return
     with torch.cuda.stream(sib):
@@ -541,15 +463,6 @@ def defer_flush_sibling(device, node_params=()):
             op.late_params.extend(node_params)
             op.recorded = True  # from here on every gradient target handed out is late (_grad_target): whatever node asks
     _LATE_USED.setdefault(device, []).append(sib)
-
-
-def defer_flush_side(device):
-    """Inside deferred_reductions: run the finishes queued so far on a side stream, beside whatever follows on the current
-    one (called where the decoders' backward is complete and the launch-latency-bound encoder backward begins)."""
-    if not DEFER_SIDE or not DEFER or device.type != "cuda" or _lib.load().mvk_defer_pending() == 0:
-        return
-    with torch.cuda.stream(_side_stream(device, 63)):
-        call("mvk_defer_flush", stream_ptr())
 
 
 # -----------------------------------------------------------------------------------------------------
@@ -584,65 +497,21 @@ def _tensors_of(obj):
             yield from _tensors_of(v)
 
 
-# Weight / bias gradients of a launch-latency-bound backward chain (the encoders at the training batch: ~20 launches of
-# 5-30 us each) are leaves: on their own stream they could run beside the backward-data chain instead of inside it.
-# MEASURED (MoPoE MnistSvhn step, hipGraph replay): 1.435 ms with the SVHN encoder's leaves on a third stream vs 1.385 ms
-# without — every fork / join edge between streams of a captured graph costs more than the ~90 us of leaf work it moves
-# off the chain (third result of this kind).  Off unless MVK_LEAF_STREAM=1.
-LEAF_STREAM = _lib.tune("MVK_LEAF_STREAM", "0") == "1"
 # MVK_WGRAD_PAIR=0: the convolutional encoder's two inner weight gradients as two launches inside the backward-data chain (A/B)
 WGRAD_PAIR = _lib.tune("MVK_WGRAD_PAIR", "1") != "0"
-# MVK_ENC_BWD_TILED (bit 0: the 64 <- 128 layer, bit 1: the 32 <- 64 layer): the convolutional encoder's backward-data launches on
-# the tiled engine when register-stationary late leaves of a decoder are in flight (big_late_leaves): a 512-register workgroup
-# waits for a CU those leaves have left, <= 128-register ones run beside them
-ENC_BWD_TILED = int(_lib.tune("MVK_ENC_BWD_TILED", "0"))
-
-
-class LeafStream:
-    """lf = LeafStream(device); `with lf:` enqueues the enclosed launches on the leaf stream, ordered behind everything
-    the current stream holds at that point; `lf.join()` orders the current stream behind the leaf stream (call it before
-    the node returns: tensors the leaf launches read may be freed afterwards).  A no-op on the CPU or with
-    MVK_LEAF_STREAM=0."""
-
-    def __init__(self, device, index=31):
-        self.on = LEAF_STREAM and device.type == "cuda"
-        self.device = device
-        self.st = _side_stream(device, index) if self.on else None
-        self._ctx = None
-        self.used = False
-
-    def __enter__(self):
-        if self.on:
-            cur = torch.cuda.current_stream(self.device)
-            self.st.wait_event(cur.record_event())
-            self._ctx = torch.cuda.stream(self.st)
-            self._ctx.__enter__()
-            self.used = True
-        return self
-
-    def __exit__(self, *exc):
-        if self._ctx is not None:
-            self._ctx.__exit__(*exc)
-            self._ctx = None
-        return False
-
-    def join(self):
-        if self.on and self.used:
-            torch.cuda.current_stream(self.device).wait_stream(self.st)
 
 
 # The decoders' side branches are CREATED before the main one (run_branches(side_first=True)), so that autograd enqueues the main
 # branch's backward first and a side branch's backward can be ordered behind the main branch's HBM-bound tail kernel
 # (tail_bwd_done / wait_tail_bwd).  Two memory-heavy launches that share the chip are slower than the same two in a row:
 # small_up_bwd_bf_kernel took 139 us beside the MLP decoder's backward-data GEMM (95 us), 82 and 32 us alone.  MEASURED (three
-# same-box pairs): 1.087 / 1.080 / 1.095 ms -> 1.040 / 1.055 / 1.050 ms.  MVK_TAIL_FIRST=0: the round-3 order.
-TAIL_FIRST = _lib.tune("MVK_TAIL_FIRST", "1") != "0"
+# same-box pairs): 1.087 / 1.080 / 1.095 ms -> 1.040 / 1.055 / 1.050 ms.
 _TAIL_EVENT = {}
 
 
 def tail_bwd_done(device):
     """SVHNDecoderFn.backward, right behind its image-layer launch."""
-    if TAIL_FIRST and device in _DEFER_ACTIVE:
+    if device in _DEFER_ACTIVE:
         _TAIL_EVENT[device] = torch.cuda.current_stream(device).record_event()
 
 
@@ -651,39 +520,6 @@ def wait_tail_bwd(device):
     ev = _TAIL_EVENT.pop(device, None)
     if ev is not None:
         torch.cuda.current_stream(device).wait_event(ev)
-
-
-# A side branch's forward LAUNCHES may be postponed behind a point of the main branch's forward (its node is created first all the
-# same): the MLP decoder's GEMMs read ~200 MB through L2 / the fabric and slow the 128 <-> 64-channel convolution of the SVHN
-# decoder (4 workgroup types, 2-2.5x fabric traffic of its own) far more than its 64 <-> 32-channel one.  MEASURED (three same-box
-# pairs): 1.060 / 1.034 / 1.048 ms postponed behind the first convolution vs 1.047 / 1.051 / 1.042 ms launched where the node is
-# created — no difference in the forward pass; MVK_FWD_DEFER=1 enables it.
-FWD_DEFER_AT = int(_lib.tune("MVK_FWD_DEFER", "0"))  # 1: behind the 128 -> 64 layer; 2: behind the 64 -> 32 layer; 3: behind the fused tail;
-# 4: behind the FIRST layer, the side branch's z-independent preparation included
-FWD_DEFER = FWD_DEFER_AT > 0
-_FWD_DEFERRED = {}  # device -> [(stream, closure)], only while run_branches(side_first=True) builds the side branches
-_FWD_DEFER_OPEN = set()
-
-
-def defer_forward(device, fn):
-    """Inside a side branch of run_branches(side_first=True): queue fn (launches only: every tensor is allocated already) until
-    the main branch calls flush_deferred_forward, or the branches are joined.  False: the caller launches now."""
-    if not FWD_DEFER or device not in _FWD_DEFER_OPEN or TAPS is not None:
-        return False
-    _FWD_DEFERRED.setdefault(device, []).append((torch.cuda.current_stream(device), fn))
-    return True
-
-
-def flush_deferred_forward(device):
-    """Main branch: the postponed side launches may start behind what this stream holds now."""
-    todo = _FWD_DEFERRED.pop(device, None)
-    if not todo:
-        return
-    ev = torch.cuda.current_stream(device).record_event()
-    for st, fn in todo:
-        st.wait_event(ev)
-        with torch.cuda.stream(st):
-            fn()
 
 
 _PRELUDE = {}  # device -> closure with launches that depend on nothing of the step (run at the head of the first side branch)
@@ -702,52 +538,32 @@ def run_prelude(device):
         fn()
 
 
-# MVK_BRANCH_MAX=n: at most n streams for the modality branches (the caller's + n - 1 side streams; branches beyond that share
-# the side streams round-robin, in order).  Five PolyMNIST stacks on five streams trample each other (cfg4: c3rs_kernel 188 us
-# average, 1326 us maximum); 0 = one stream per branch.
-BRANCH_MAX = int(_lib.tune("MVK_BRANCH_MAX", "0"))
-
-
-def _branch_stream(device, i, n):
-    """The stream of branch i (i >= 1) of n."""
-    if BRANCH_MAX >= 2 and n > BRANCH_MAX:
-        i = 1 + (i - 1) % (BRANCH_MAX - 1)
-    return _side_stream(device, i)
-
-
 def run_branches(names, fn, device, side_first=False):
     """{m: fn(m)} with every branch but the first on its own stream; joined before returning."""
     names = list(names)
     if not BRANCH_STREAMS or len(names) < 2 or device.type != "cuda":
         return {m: fn(m) for m in names}
     main = torch.cuda.current_stream(device)
-    _BRANCH_SET[device] = [main] + list(dict.fromkeys(_branch_stream(device, i, len(names)) for i in range(1, len(names))))
+    _BRANCH_SET[device] = [main] + [_side_stream(device, i) for i in range(1, len(names))]
     fork = main.record_event()
     # The first branch stays on the caller's stream and is enqueued FIRST: autograd runs backward nodes in reverse
     # creation order, so the side branches' backward is enqueued (and, in a captured graph, ordered) before the long
     # backward of the main branch instead of behind it.
     outs = {}
-    if not (side_first and TAIL_FIRST):
+    if not side_first:
         outs[names[0]] = fn(names[0])
-    else:
-        _FWD_DEFER_OPEN.add(device)
     sides = []
     for i, m in enumerate(names[1:], start=1):
-        st = _branch_stream(device, i, len(names))
-        if st not in sides:
-            st.wait_event(fork)
-            sides.append(st)
+        st = _side_stream(device, i)
+        st.wait_event(fork)
+        sides.append(st)
         with torch.cuda.stream(st):
             run_prelude(device)
             outs[m] = fn(m)
         for t in _tensors_of(outs[m]):
             t.record_stream(main)
-    if names[0] not in outs:
-        _FWD_DEFER_OPEN.discard(device)  # the main branch itself never defers
-        try:
-            outs[names[0]] = fn(names[0])
-        finally:
-            flush_deferred_forward(device)  # nobody asked for them earlier: now
+    if side_first:
+        outs[names[0]] = fn(names[0])
     for st in sides:
         main.wait_stream(st)
     return {m: outs[m] for m in names}
@@ -844,24 +660,6 @@ def heads_fwd(h2, w_mu, b_mu, w_lv, b_lv, N, w_sk, w_sn):
     return mu, lv
 
 
-# MVK_NARROW_DZ=1: the decoders' gradient into the latent (N = L <= 32 outputs from K = 512 / 2048 over the decoder batch) as ONE
-# exact-fp32 launch that reads its input once (narrow_linear / narrow_fwd_kernel) instead of a split-K launch of the tiled engine +
-# its reduce.  MEASURED (four alternating pairs): 0.9382 / 0.9361 / 0.9307 / 0.9317 ms with, 0.9361 / 0.9288 / 0.9293 / 0.9271
-# without (+0.4 %): the launch takes 21.5 / 28.7 us in the step beside the last decoder launches, no less than the pair it
-# replaces (18.5 + 4.5 / 18.5 + 9).  Off.
-NARROW_DZ = _lib.tune("MVK_NARROW_DZ", "0") == "1"
-
-
-def narrow_linear(x2, w, M, N, K, w_sk, w_sn):
-    """y[M, N] = x2[M, K] W with W(k, n) = w[k * w_sk + n * w_sn], 16 < N <= 32, M >= 1024 rows: ONE launch that reads x2 once
-    (mvk_heads_fwd's one-head, many-rows form: narrow_fwd_kernel, exact fp32, fixed summation order).  None: not covered."""
-    if not NARROW_DZ or not (16 < N <= 32) or K % 4 != 0 or M < 1024 or x2.data_ptr() % 16 != 0 or not x2.is_cuda:
-        return None
-    y = _new((M, N), x2)
-    call("mvk_heads_fwd", ptr(x2), ptr(w), None, ptr(y), None, None, None, M, N, K, w_sk, w_sn, stream_ptr())
-    return y
-
-
 HEADS_BWD = _lib.tune("MVK_HEADS_BWD", "1") != "0"  # A/B switch: the heads' backward in one launch
 # MEASURED (headline step, one box, 3-4 rounds each): 1.355 ms with the six separate launches, 1.326 ms with the fused launch
 # for the convolutional (SVHN) encoder only, 1.343 ms with the fused launch for the MLP encoder too (its chain is not the
@@ -946,13 +744,6 @@ def wfrag(w):
 
 
 PACK_MAX = 16  # MVK_PACK_MAX descriptors per launch
-# MVK_PREPACK=0: every network packs its own weights when it runs (one launch per network and forward pass)
-PREPACK = _lib.tune("MVK_PREPACK", "1") != "0"
-# MVK_PACK_SIDE=1: the pack launch on the first branch stream, beside the image-consuming first convolution (which reads the
-# reference weight layout).  MEASURED (three same-box pairs): 1.074 / 1.079 / 1.074 ms without vs 1.137 / 1.130 / 1.131 ms with —
-# one more fork / join edge at the head of the captured graph costs three times the 20 us it takes off the chain (the fourth result
-# of this kind: DESIGN.md section 9).  Off.
-PACK_SIDE = _lib.tune("MVK_PACK_SIDE", "0") == "1"
 _PACK_SCOPE = None
 
 
@@ -967,7 +758,7 @@ class pack_scope:
 
     def __enter__(self):
         global _PACK_SCOPE
-        if PREPACK and _PACK_SCOPE is None:
+        if _PACK_SCOPE is None:
             _PACK_SCOPE = {"model": self.model, "cache": {}, "done": False}
             self.own = True
             # the zeroed arena of the amax protocol (AmaxPool, the pack launches): filled HERE, on the caller's stream and in front
@@ -976,43 +767,7 @@ class pack_scope:
             dev = next((p.device for p in self.model.parameters()), None)
             if (C3_F16 or IMG_F16) and dev is not None and dev.type == "cuda":
                 _PACK_SCOPE["amax"], _PACK_SCOPE["amax_pos"] = torch.zeros(512, dtype=torch.float32, device=dev), 0
-            if PACK_SIDE and BRANCH_STREAMS and dev is not None and dev.type == "cuda":
-                self._launch_beside(dev)
-        if _ROTATE_ARMED:  # a rotated step's head branch forks HERE, behind the first launch of the main chain
-            for r in list(_ROTATE_ARMED.values()):
-                r.begin_if_armed()
         return self
-
-    def _launch_beside(self, dev):
-        """The step's ONE weight-pack launch on the first branch stream, beside the first kernels of the forward pass (the image-
-        consuming first convolution reads the reference layout: `mvk_conv4s2_small_down_fwd_wref`), instead of in front of
-        them on the caller's stream: 20 us of the launch-latency-bound head of the step.  A stream that takes a pack out of the
-        cache orders itself behind the launch once (`pack_weights`)."""
-        sc = _PACK_SCOPE
-        jobs, keys = [], []
-        for mod in self.model.modules():
-            announce = getattr(mod, "pack_jobs", None)
-            if announce is None:
-                continue
-            for j in announce():
-                k = _job_key(j)
-                if k not in keys and j[0].device == dev:
-                    jobs.append(j)
-                    keys.append(k)
-        sc["done"] = True
-        if not jobs:
-            return
-        main = torch.cuda.current_stream(dev)
-        st = _side_stream(dev, 1)
-        st.wait_event(main.record_event())  # behind the optimizer step that wrote the weights, and the amax arena's fill
-        with torch.cuda.stream(st):
-            outs = []
-            for i0 in range(0, len(jobs), PACK_MAX):
-                outs += _pack_launch(jobs[i0:i0 + PACK_MAX])
-            sc["event"] = st.record_event()
-        sc["pack_stream"], sc["waited"] = st, {st.cuda_stream}
-        for k, o in zip(keys, outs):
-            sc["cache"][k] = o
 
     def __exit__(self, *exc):
         global _PACK_SCOPE
@@ -1042,16 +797,6 @@ def pack_weights(jobs):
         return _pack_launch(jobs)
     cache = sc["cache"]
     if all(k in cache for k in keys):
-        ev = sc.get("event")
-        if ev is not None:  # packed on another stream (pack_scope._launch_beside): this stream waits for it once
-            cur = torch.cuda.current_stream(jobs[0][0].device)
-            if cur.cuda_stream not in sc["waited"]:
-                cur.wait_event(ev)
-                sc["waited"].add(cur.cuda_stream)
-                for t in _tensors_of([cache[k] for k in cache if not (isinstance(k, tuple) and k and k[0] in ("dense16", "dense16_xamax"))]):
-                    t.record_stream(cur)
-                    if getattr(t, "mvk_frag", None) is not None:
-                        t.mvk_frag.record_stream(cur)
         return [cache[k] for k in keys]
     todo, tkeys = list(jobs), list(keys)
     if not sc["done"]:
@@ -1156,11 +901,8 @@ def conv_down(U, wdown, bias, n, h, w, Cu, Cv, act=NONE, u_nchw=False, u_act_src
     return V if out_bias is None else (V, rb)
 
 
-FMT_TILED = 2  # mvk.h MVK_FMT_TILED
-
-
 def conv_up(V, wup, bias, n, h, w, Cu, Cv, act=NONE, u_nchw=False, u_act_src=None, u_act=NONE, out_bias=None,
-            in_bf3=False, frag=None, amax=None, out=None, tiled=False):
+            in_bf3=False, frag=None, amax=None, out=None):
     U = out if out is not None else torch.empty((n, Cu, 2 * h, 2 * w) if u_nchw else (n, 2 * h, 2 * w, Cu), dtype=torch.float32,
                                                 device=V.device)
     ws = _ws(U)
@@ -1173,7 +915,7 @@ def conv_up(V, wup, bias, n, h, w, Cu, Cv, act=NONE, u_nchw=False, u_act_src=Non
              stream_ptr())
         return U if out_bias is None else (U, rb)
     call("mvk_conv4s2_up", ptr(V), ptr(wup), ptr(bias), ptr(U), n, h, w, Cu, Cv, act, int(u_nchw),
-         ptr(u_act_src), u_act, ptr(tb), ptr(ws), ws.numel(), (FMT_IN_BF3 if in_bf3 else 0) | (FMT_TILED if tiled else 0),
+         ptr(u_act_src), u_act, ptr(tb), ptr(ws), ws.numel(), FMT_IN_BF3 if in_bf3 else 0,
          ptr(frag if frag is not None else wfrag(wup)), stream_ptr())
     return U if out_bias is None else (U, rb)
 
@@ -1245,7 +987,7 @@ IMG_F16_MIN_ROWS = 1024
 def _amax_slots(like, n, create=False):
     """n zeroed device scalars.  Inside a pack_scope they are carved from the ONE arena the scope filled when it was entered
     (in front of every stream fork of the forward pass): one fill per forward pass instead of one per pool, all of them on
-    the step's critical chain.  Outside a scope (backward passes, PREPACK off): a fill on the current stream."""
+    the step's critical chain.  Outside a scope (backward passes): a fill on the current stream."""
     sc = _PACK_SCOPE
     if sc is not None:
         ar = sc.get("amax")
@@ -1636,7 +1378,7 @@ def _planes(rows, cols, like):
     return t, t[0], t[1]
 
 
-def dense16_pack(w, raw=False, defer=None):
+def dense16_pack(w, raw=False):
     """Planes of a Linear weight [N][K] in both orientations + the per-row inverse scales; once per forward pass inside a
     pack_scope (the cache dies with the scope: the weights change at the next optimizer step).  raw: launch here, no cache."""
     sc = _PACK_SCOPE
@@ -1650,31 +1392,21 @@ def dense16_pack(w, raw=False, defer=None):
     N, K = w.shape
     nk, kn = _planes(N, K, w), _planes(K, N, w)
     nk_inv, kn_inv = _new((N,), w), _new((K,), w)
-
-    def go():
-        call("mvk_dense16_pack", ptr(w), N, K, ptr(nk[1]), ptr(nk[2]), ptr(nk_inv), ptr(kn[1]), ptr(kn[2]), ptr(kn_inv), stream_ptr())
-
-    if defer is not None:
-        defer.append(go)  # (the caller launches it: MLPDecoderFn with MVK_FWD_DEFER=4)
-    else:
-        go()
+    call("mvk_dense16_pack", ptr(w), N, K, ptr(nk[1]), ptr(nk[2]), ptr(nk_inv), ptr(kn[1]), ptr(kn[2]), ptr(kn_inv), stream_ptr())
     out = (nk, nk_inv, kn, kn_inv)
     if sc is not None and not raw:
         sc["cache"][key] = out
     return out
 
 
-def dense16_xamax(x, defer=None):
+def dense16_xamax(x):
     """Device scalar >= max |x| of a target batch, once per forward pass inside a pack_scope."""
     sc = _PACK_SCOPE
     key = ("dense16_xamax", x.data_ptr(), tuple(x.shape))
     if sc is not None and key in sc["cache"]:
         return sc["cache"][key]
     slot = _amax_slots(x, 1)
-    if defer is not None:
-        defer.append(lambda: call("mvk_amax", ptr(x), x.numel(), ptr(slot), stream_ptr()))
-    else:
-        call("mvk_amax", ptr(x), x.numel(), ptr(slot), stream_ptr())
+    call("mvk_amax", ptr(x), x.numel(), ptr(slot), stream_ptr())
     if sc is not None:
         sc["cache"][key] = slot
     return slot
@@ -1747,11 +1479,8 @@ class MLPDecoderFn(Function):
             if ROT_MLP != 1:
                 rot = None
             rkey = ("mlp_dec", w0.data_ptr(), n)
-            # MVK_FWD_DEFER=4: this branch's z-independent preparation joins the postponed launches (flushed behind the large
-            # decoder's FIRST layer, the latency-sized launch on the step's chain these 30 us of launches otherwise run beside)
-            prep = [] if (FWD_DEFER_AT == 4 and z2.device in _FWD_DEFER_OPEN and TAPS is None) else None
-            nk, nk_inv, kn, kn_inv = dense16_pack(w1, defer=prep)  # both usually done already: Decoder_AE_MLP.early_work
-            xam = dense16_xamax(nll_x, defer=prep)
+            nk, nk_inv, kn, kn_inv = dense16_pack(w1)
+            xam = dense16_xamax(nll_x)
             zam = _amax_slots(z2, 1)
             lib = _lib.load()
             P, CR = lib.mvk_dense16_fwd_nll_rows(D), lib.mvk_dense16_colsum_rows(n)
@@ -1769,19 +1498,12 @@ class MLPDecoderFn(Function):
                 bounds = rot.buf(rkey + ("bounds",), (2,))
                 cs = rot.buf(rkey + ("cs",), (CR, D))
             rows = _new((P, n), z2)
-
-            def launch():  # the three launches of the forward pass (possibly postponed: defer_forward)
-                for f in prep or ():
-                    f()
-                call("mvk_amax", ptr(z2), z2.numel(), ptr(zam), stream_ptr())
-                call("mvk_dense16_first", ptr(z2), ptr(w0), ptr(b0), ptr(zam), ptr(hp[1]), ptr(hp[2]), ptr(bounds[0:1]), n, H, L,
-                     RELU, stream_ptr())
-                call("mvk_dense16_fwd_nll", ptr(hp[1]), ptr(hp[2]), ptr(bounds[0:1]), ptr(nk[1]), ptr(nk[2]), ptr(nk_inv), ptr(b1),
-                     ptr(nll_x), nll_x.shape[0], ptr(xam), float(nll_scale), float(nll_weight), ptr(gp[1]), ptr(gp[2]),
-                     ptr(bounds[1:2]), ptr(rows), ptr(cs), n, D, H, stream_ptr())
-
-            if not defer_forward(z2.device, launch):
-                launch()
+            call("mvk_amax", ptr(z2), z2.numel(), ptr(zam), stream_ptr())
+            call("mvk_dense16_first", ptr(z2), ptr(w0), ptr(b0), ptr(zam), ptr(hp[1]), ptr(hp[2]), ptr(bounds[0:1]), n, H, L,
+                 RELU, stream_ptr())
+            call("mvk_dense16_fwd_nll", ptr(hp[1]), ptr(hp[2]), ptr(bounds[0:1]), ptr(nk[1]), ptr(nk[2]), ptr(nk_inv), ptr(b1),
+                 ptr(nll_x), nll_x.shape[0], ptr(xam), float(nll_scale), float(nll_weight), ptr(gp[1]), ptr(gp[2]),
+                 ptr(bounds[1:2]), ptr(rows), ptr(cs), n, D, H, stream_ptr())
             ctx.save_for_backward(z2, hp[0], gp[0], bounds, kn[0], kn_inv, cs, w0, b0, w1, b1)
             ctx.nll_weight = float(nll_weight)
             if TAPS is not None:  # tests: the hidden activation as an fp32 tensor (the sign of h is the sign of its hi plane)
@@ -1840,8 +1562,7 @@ class MLPDecoderFn(Function):
             # the gradient of z first (the posterior's backward waits for it), the weight gradients — leaves — behind it
             dz = None
             if ctx.needs_input_grad[0]:
-                dz = narrow_linear(dh, w0, n, w0.shape[1], H, w0.shape[1], 1)  # W(k = h, l) = w0[h][l]
-                dz = (dz if dz is not None else linear_bwd_data(dh, w0)).view(ctx.z_shape)
+                dz = linear_bwd_data(dh, w0).view(ctx.z_shape)
 
             def wgrad1():
                 wsl = _ws(z2)
@@ -1859,13 +1580,13 @@ class MLPDecoderFn(Function):
                 rot.push(leaves, (w1, b1, w0), prepare)
                 return dz, None, db0, None, None, None, None, None, None
 
-            # a leaf: postponed into the tail of the step when its targets are views of the flat gradient buffer
-            if dw1 is not None or db1 is not None or not run_last(z2.device, wgrad1, gp, hp, cs, bounds, params=(w1, b1)):
-                wgrad1()
+            wgrad1()
+            # the first layer's weight gradient, a leaf: postponed into the tail of the step when its target is a view of the flat
+            # gradient buffer (run_last)
             dw0 = None
             if rot0 is not None:  # mode 2: the first layer's weight gradient is the head of the next step (z2 is the fixed copy)
                 rot0.push(lambda: linear_bwd_weight(dh, z2, w0, None), (w0,), None)
-            elif not _is_direct(w0) or not run_last(z2.device, lambda: linear_bwd_weight(dh, z2, w0, None), dh, z2, force=LATE_DW0, params=(w0,)):
+            elif not _is_direct(w0) or not run_last(z2.device, lambda: linear_bwd_weight(dh, z2, w0, None), dh, z2, params=(w0,)):
                 dw0, _ = linear_bwd_weight(dh, z2, w0, None)
             return dz, dw0, db0, dw1, db1, None, None, None, None
         else:  # general upstream gradient: d pre = G * drows[column tile, row] / nll_weight as an fp32 tensor, then the tiled engine
@@ -1882,9 +1603,7 @@ class MLPDecoderFn(Function):
         dz = None
         if ctx.needs_input_grad[0]:
             dz = linear_bwd_data(dh, w0).view(ctx.z_shape)
-        dw0 = None
-        if not _is_direct(w0) or not run_last(z2.device, lambda: linear_bwd_weight(dh, z2, w0, None), dh, z2, params=(w0,)):
-            dw0, _ = linear_bwd_weight(dh, z2, w0, None)
+        dw0, _ = linear_bwd_weight(dh, z2, w0, None)
         return dz, dw0, db0, dw1, db1, None, None, None, None
 
 
@@ -1940,7 +1659,6 @@ class SVHNEncoderFn(Function):
         defer_flush_sibling(x.device, node_params=(w0, b0, w1, b1, w2, b2, wc1, bc1, wc2, bc2))
         # heads: both weight gradients (in the Conv2d layout), both bias gradients, d h3 (pre-activation: dmu Wd1^T + dlv Wd2^T
         # with ReLU'(h3)) and its channel sums (the bias gradient of the layer below) in one launch
-        lf = LeafStream(x.device)  # the weight / bias gradients run beside the backward-data chain
         fused = heads_bwd(h3f, RELU, [dmu, dlv], [wdc1, wdc2], [bc1, bc2], L, 1, flat_c=ch[3], prev_bias=b2,
                           dw_params=[wc1, wc2]) if (H // 8, W // 8) == (4, 4) else None
         if fused is not None:
@@ -1948,43 +1666,36 @@ class SVHNEncoderFn(Function):
         else:
             tw1, dwc1 = _grad_target(wc1)
             tw2, dwc2 = _grad_target(wc2)
-            with lf:
-                ws = _ws(x)
-                call("mvk_flatten_wgrad", ptr(h3f), ptr(dmu), ptr(tw1), B, ch[3], L, ptr(ws), ws.numel(), stream_ptr())
-                call("mvk_flatten_wgrad", ptr(h3f), ptr(dlv), ptr(tw2), B, ch[3], L, ptr(ws), ws.numel(), stream_ptr())
-                dbc1, dbc2 = colsum(dmu, bc1), colsum(dlv, bc2)
+            ws = _ws(x)
+            call("mvk_flatten_wgrad", ptr(h3f), ptr(dmu), ptr(tw1), B, ch[3], L, ptr(ws), ws.numel(), stream_ptr())
+            call("mvk_flatten_wgrad", ptr(h3f), ptr(dlv), ptr(tw2), B, ch[3], L, ptr(ws), ws.numel(), stream_ptr())
+            dbc1, dbc2 = colsum(dmu, bc1), colsum(dlv, bc2)
             dh3 = gemm(dmu, wdc1, B, Kf, L, tb=True, c_act_src=h3f, c_act=RELU)
             gemm(dlv, wdc2, B, Kf, L, tb=True, c_act_src=h3f, c_act=RELU, out=dh3, accumulate=True)
         dh3 = dh3.view(B, H // 8, W // 8, ch[3])
         # The two inner layers' weight gradients as ONE launch behind both backward-data launches (mvk_conv4s2_wgrad_pair): at the
         # training batch each is a split-K GEMM of 256 workgroups and ~35 us, and the four launches were one dependent chain
         # (the step's last one).  Only where both targets are views of the flat gradient buffer inside deferred_reductions (the
-        # pair's slabs live in the arena) and the leaf stream is off.
-        pair = (WGRAD_PAIR and not lf.on and x.device in _DEFER_ACTIVE and _is_direct(w1) and _is_direct(w2)
+        # pair's slabs live in the arena).
+        pair = (WGRAD_PAIR and x.device in _DEFER_ACTIVE and _is_direct(w1) and _is_direct(w2)
                 and x.device.type == "cuda")
         if not pair:
-            with lf:
-                dw2 = conv_wgrad(h2, dh3, w2, B, H // 8, W // 8, ch[2], ch[3])
+            dw2 = conv_wgrad(h2, dh3, w2, B, H // 8, W // 8, ch[2], ch[3])
         if fused is None:
-            with lf:
-                db2 = colsum(dh3.view(-1, ch[3]), b2)
+            db2 = colsum(dh3.view(-1, ch[3]), b2)
         # each backward-data launch also emits the bias gradient of the layer it lands in (column sums of its output)
         dh2, db1 = conv_up(dh3, wu2, None, B, H // 8, W // 8, ch[2], ch[3], u_act_src=h2, u_act=RELU, out_bias=b1,
-                           frag=ctx.frags[1], tiled=bool(ENC_BWD_TILED & 1) and x.device in _BIG_LATE)
+                           frag=ctx.frags[1])
         if not pair:
-            with lf:
-                dw1 = conv_wgrad(h1, dh2, w1, B, H // 4, W // 4, ch[1], ch[2])
+            dw1 = conv_wgrad(h1, dh2, w1, B, H // 4, W // 4, ch[1], ch[2])
         dh1, db0 = conv_up(dh2, wu1, None, B, H // 4, W // 4, ch[1], ch[2], u_act_src=h1, u_act=RELU, out_bias=b0,
-                           frag=ctx.frags[0], tiled=bool(ENC_BWD_TILED & 2) and x.device in _BIG_LATE)
-        late_gate(x.device)  # the decoder's gated late leaves (MVK_LATE_GATE) may start: no 512-register launch of this chain is left
+                           frag=ctx.frags[0])
         if pair:
             ws = _ws(x)
             call("mvk_conv4s2_wgrad_pair", ptr(h2), ptr(dh3), ptr(_grad_target(w2)[0]), H // 8, W // 8, ch[2], ch[3],
                  ptr(h1), ptr(dh2), ptr(_grad_target(w1)[0]), H // 4, W // 4, ch[1], ch[2], B, ptr(ws), ws.numel(), stream_ptr())
             dw2 = dw1 = None
-        with lf:
-            dw0 = conv_wgrad(x, dh1, w0, B, H // 2, W // 2, ch[0], ch[1], u_nchw=True)
-        lf.join()
+        dw0 = conv_wgrad(x, dh1, w0, B, H // 2, W // 2, ch[0], ch[1], u_nchw=True)
         dx = None
         if ctx.needs_input_grad[0]:
             raise _lib.MvkError("gradient w.r.t. the encoder input image is not implemented")
@@ -2056,15 +1767,9 @@ class SVHNDecoderFn(Function):
             else:
                 gemm(z2, wp0, n, 16 * C1, L, bias=b0, bias_mod=C1, act=RELU, out=g1)
                 amax_of(g1, a1)
-            if FWD_DEFER_AT == 4:
-                flush_deferred_forward(z2.device)  # a side branch's postponed launches: behind the first (latency-sized) layer
             g2 = conv_up(g1, wu1, b1, n, 4, 4, C2, C1, RELU, amax=(a1, wu1.mvk_amax, a2),
                          out=None if rot is None else rot.buf(rkey + ("g2",), (n, 8, 8, C2)))  # [n,8,8,C2]
-            if FWD_DEFER_AT <= 1:
-                flush_deferred_forward(z2.device)  # a side branch's postponed launches: beside the 64 -> 32 layer, not the 128 -> 64 one
             g3 = conv_up(g2, wu2, b2, n, 8, 8, C3, C2, RELU, amax=(a2, wu2.mvk_amax, a3))  # [n,16,16,C3]
-            if FWD_DEFER_AT == 2:
-                flush_deferred_forward(z2.device)  # ... beside the fused tail (HBM-bound: the other resource)
             ctx.wamax = (wd1.mvk_amax, wd2.mvk_amax)
             ctx.gamax = (a1, a2)  # bounds of g1, g2: the V operands of the two weight gradients
         else:
@@ -2213,17 +1918,9 @@ class SVHNDecoderFn(Function):
                 dz = _svhn_dz(dg1f, wp0, n, L, C1).view(ctx.z_shape)
             dg2.record_stream(_side_stream(z2.device, 30))
             dg1.record_stream(_side_stream(z2.device, 30))
-            def big_leaves():
-                conv_wgrad(dg3, g2, w2, n, 8, 8, C3, C2, amax=wam2)
-                conv_wgrad(dg2, g1, w1, n, 4, 4, C2, C1, amax=wam1)
-
-            gated_ok = (LATE_GATE and ctx.f16 and wam1 is not None and not SKIP_LATE and _is_direct(w1) and _is_direct(w2)
-                        and run_gated(z2.device, big_leaves, dg3, g2, dg2, g1))
             with late:
-                dw2 = dw1 = None
-                if not SKIP_LATE and not gated_ok:
-                    dw2 = conv_wgrad(dg3, g2, w2, n, 8, 8, C3, C2, amax=wam2)
-                    dw1 = conv_wgrad(dg2, g1, w1, n, 4, 4, C2, C1, amax=wam1)
+                dw2 = conv_wgrad(dg3, g2, w2, n, 8, 8, C3, C2, amax=wam2)
+                dw1 = conv_wgrad(dg2, g1, w1, n, 4, 4, C2, C1, amax=wam1)
                 if rot0 is not None:
                     # mode 2: the first layer's weight gradient (a split-K GEMM over z and dg1) is the head of the next step; z is
                     # copied to a buffer with a fixed address HERE, on the late-leaf stream (off the backward chain)
@@ -2254,8 +1951,7 @@ class SVHNDecoderFn(Function):
 
 def _svhn_dz(dg1f, wp0, n, L, C1):
     """d z = d g1 W0^T of the SVHN decoder's first layer (wp0: the [L][16 C1] unflatten pack)."""
-    y = narrow_linear(dg1f, wp0, n, L, 16 * C1, 1, 16 * C1)
-    return y if y is not None else gemm(dg1f, wp0, n, L, 16 * C1, tb=True)
+    return gemm(dg1f, wp0, n, L, 16 * C1, tb=True)
 
 
 def svhn_fused_tail_ok(C4, C3):
@@ -2571,7 +2267,6 @@ class MoPoEPosteriorFn(Function):
         dz = _c(dz) if dz is not None else torch.zeros_like(eps)
         dmus = [_new((B, L), eps) for _ in range(M)]
         dlvs = [_new((B, L), eps) for _ in range(M)]
-        defer_flush_side(eps.device)  # the decoders are done: finish their gradients beside the encoder backward
         call("mvk_mopoe_posterior_bwd", ptr_array(mus), ptr_array(lvs), M, ptr(subset_masks), subset_masks.numel(),
              ptr(sel), ptr(ctx.weights), ptr(eps), ptr(dz), K, B, L, ptr(gk), ptr_array(dmus), ptr_array(dlvs),
              stream_ptr())
@@ -2679,25 +2374,16 @@ def unit_seed(like):
     return t
 
 
-UNIT_SEED = _lib.tune("MVK_UNIT_SEED", "1") != "0"  # 0: always launch the seed kernel (A/B)
-
-
 def is_unit_seed(g):
-    if not UNIT_SEED:
-        return False
     t = _UNIT_SEEDS.get(g.data_ptr())
     return t is not None and t.shape == g.shape and t.device == g.device
 
 
-TERMS_MULTI_WG = _lib.tune("MVK_TERMS_WS", "1") != "0"  # 0: the one-workgroup launch (A/B)
 _TERMS_WS = {}  # (device, stream) -> the arrival counter + partials of mvk_reduce_terms_ws (zero between launches)
 
 
 def _reduce_terms(terms, n_terms, loss_sum_scale, out, loss):
     """The scalar assembly on the current stream, on several workgroups where a term is long (mvk_reduce_terms_ws)."""
-    if not TERMS_MULTI_WG:
-        call("mvk_reduce_terms", terms, n_terms, loss_sum_scale, ptr(out), ptr(loss), stream_ptr())
-        return
     key = (out.device, torch.cuda.current_stream(out.device).cuda_stream)
     ws = _TERMS_WS.get(key)
     if ws is None:
@@ -2717,7 +2403,7 @@ def terms_workspace(device, stream):
     """Make the assembly's workspace of (device, stream) now, outside any capture (trainers/graph.py: before torch.cuda.graph, for
     the capture stream and the late-leaf stream the assembly may run on).  Eager memory, zeroed once, left zero by every launch."""
     key = (device, stream.cuda_stream)
-    if key not in _TERMS_WS and TERMS_MULTI_WG:
+    if key not in _TERMS_WS:
         _TERMS_WS[key] = torch.zeros(1 + 32 * 64, dtype=torch.float32, device=device)
 
 
@@ -2836,7 +2522,7 @@ class ReconLossFn(Function):
                 for t in keep:
                     t.record_stream(st)
 
-            if run_last(dev, assemble, *extras, force=True):
+            if run_last(dev, assemble, *extras):
                 _LOSS_POSTPONED[dev] = assemble
             else:
                 assemble()

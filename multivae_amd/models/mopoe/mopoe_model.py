@@ -18,16 +18,6 @@ from ..base.base_utils import ModelOutput
 from .mopoe_config import MoPoEConfig
 
 
-_EARLY_NOISE = _lib.tune("MVK_EARLY_NOISE", "1") != "0"  # 0: draw the noise behind the encoders (A/B)
-# MVK_ENC_SIDE_FIRST=1: the short encoder's node is created FIRST, so that autograd enqueues the LONG encoder's backward first (its
-# launches are the step's last chain; A/B)
-_ENC_SIDE_FIRST = kernels._lib.tune("MVK_ENC_SIDE_FIRST", "0") == "1"
-
-
-# 1: the fused decoder tails' z-independent preparation (dense16 pack + target bound, 18 us) behind the short encoder instead of in
-# the decoder's own chain.  Off since round 5: the short encoder's branch had become the LONGER one (117 vs 109 us at the join in
-# front of the posterior); in the MLP decoder's chain the two launches sit in slack.  1.0205-1.0238 -> 1.0090-1.0148 ms, four pairs.
-_EARLY_DENSE = _lib.tune("MVK_EARLY_DENSE", "0") == "1"
 _ROW_WEIGHT = {}
 
 
@@ -136,23 +126,19 @@ class MoPoE(BaseMultiVAE):
                 side_work()  # BEHIND the short encoder: its stream also carries the step's weight-pack launch (kernels.pack_scope)
             return out
 
-        enc = kernels.run_branches(names, run, inputs.data[names[0]].device, side_first=_ENC_SIDE_FIRST)
+        enc = kernels.run_branches(names, run, inputs.data[names[0]].device)
         return {m: enc[m] for m in self.encoders.keys()}
 
     def _posterior(self, inputs, K, noise=None, choice=None, want_stats=False):
         early = {}
         x0 = next(iter(inputs.data.values()))
         if noise is None and x0.is_cuda and kernels.DEVICE_RNG and kernels.BRANCH_STREAMS and len(self.encoders) > 1 \
-                and x0.dim() > 1 and _EARLY_NOISE:
+                and x0.dim() > 1:
             # the noise does not depend on the encoders: its launch rides at the head of the short encoder's branch stream
             # instead of sitting between the encoders and the posterior kernel on the main one
             shape = (K, x0.shape[0], self.latent_dim)
             def side_work():
                 early.setdefault("eps", self._noise(shape, x0.device))
-                if self.fused_decoder_tail and _EARLY_DENSE and not hasattr(inputs, "masks") and self.training:
-                    for m, dec in self.decoders.items():  # z-independent preparation of the fused decoder tails
-                        if hasattr(dec, "early_work") and self.recon_dists[m][0] == kernels.DIST["normal"]:
-                            dec.early_work(inputs.data[m], K * x0.shape[0])
 
             enc = self.modality_encode(inputs, side_work=side_work)
             if "eps" in early:  # allocated on the side stream, consumed on this one (behind the join of run_branches)

@@ -34,11 +34,6 @@ from .. import _lib, kernels
 from ..data.datasets.base import DatasetOutput
 
 
-# MVK_ADAM_PRELUDE=0: the optimizer's scalar preparation directly in front of the update (end of the chain) instead of at the
-# head of a side branch (A/B)
-_ADAM_PRELUDE = _lib.tune("MVK_ADAM_PRELUDE", "1") != "0"
-
-
 class GraphedStep:
     def __init__(self, model, flat, inputs, noise=None, warmup=3, capture_error_mode="global", optimizer=None, overlap=False,
                  rotate=None, **fwd_kwargs):
@@ -124,7 +119,7 @@ class GraphedStep:
             kw["noise"] = self.noise
         dev = self.flat.flat.device
         opt = self.optimizer if capture else None  # the eager warm-up passes must not move the parameters
-        if opt is not None and _ADAM_PRELUDE:
+        if opt is not None:
             kernels.set_prelude(dev, opt.prepare_captured)  # depends on nothing of the step: head of the first side branch
         if self.overlap_point is not None:
             self.overlap_point.begin()
@@ -132,14 +127,12 @@ class GraphedStep:
         try:
             with kernels.deferred_reductions(self.flat):
                 if rot is not None:  # the head branch: the previous step's leaves, finishes, update, packs
-                    (rot.arm if kernels.ROT_ARM else rot.begin_step)(self.rot_opt.rot_update if (capture and self.rotated) else None)
+                    rot.begin_step(self.rot_opt.rot_update if (capture and self.rotated) else None)
                 out = self.model(self.inputs, **kw)
                 # the registered unit seed: filled once (not one launch per replay), and ReconLossFn.backward launches nothing
                 out.loss.backward(gradient=kernels.unit_seed(out.loss))
             if opt is not None:
                 kernels.run_prelude(dev)  # no branch took it: here, in front of the update
-                if not _ADAM_PRELUDE:
-                    opt.prepare_captured()
                 opt.step_captured()
         finally:
             kernels._PRELUDE.pop(dev, None)
