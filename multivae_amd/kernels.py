@@ -9,13 +9,11 @@ multiplies by the previous layer's activation derivative and writes the pre-acti
 import ctypes as C
 import math
 
-import os
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, schedule
 from ._lib import ACT, DIST, FAMILY, PackDesc, ReconDesc, SeedDesc, TermDesc, call, ptr, ptr_array, stream_ptr
 
 RELU, SIGMOID, NONE = ACT["relu"], ACT["sigmoid"], ACT["none"]
@@ -25,6 +23,17 @@ RELU, SIGMOID, NONE = ACT["relu"], ACT["sigmoid"], ACT["none"]
 PROFILE = {}
 # accumulate parameter gradients directly into pre-existing .grad buffers (see _grad_target)
 DIRECT_GRAD = True
+# The host scheduler (streams, the per-step scope, the switches that go with them) is schedule.py and is named as such here and
+# by every caller: no second binding of a name somebody patches or assigns.  Two plain aliases: the scope, under the name the
+# benchmark enters it by, and the scratch helper.
+deferred_reductions = schedule.deferred_reductions
+_ws = schedule._ws  # the per-stream split-K scratch every launch helper below hands to its kernel
+
+# Device-lifetime caches of this module (like those of schedule.py: made on first use, kept for the life of the process; captured
+# graphs hold their addresses).  Nothing of ONE step is kept here: that is the scope's (schedule.deferred_reductions).
+_RNG = {}  # device -> [state tensor (3 x int64: seed, offset, ticket), torch seed it was built from, breadcrumb offset]
+_UNIT_SEEDS = {}  # data_ptr -> tensor (kept alive): backward seeds known to hold exactly 1
+_CONST_GRADS = {}  # data_ptr -> (weakref of the tensor, numel, value): gradient buffers known to hold ONE constant
 
 
 def _c(t):
@@ -52,521 +61,8 @@ def to_bf3(x):
     return out
 
 
-_WS = {}
-WS_FLOATS = 16 * 1024 * 1024  # 64 MB of split-K slab scratch per device (largest need on the path: 8.4M floats)
-
-
-def _ws(like):
-    """Caller-owned split-K scratch (see mvk.h): one persistent buffer per (device, stream), reused by every launch
-    on that stream (launches are stream-ordered, so reuse is safe; two streams must not share one)."""
-    key = (like.device, torch.cuda.current_stream(like.device).cuda_stream)
-    t = _WS.get(key)
-    if t is None:
-        t = torch.empty(WS_FLOATS, dtype=torch.float32, device=like.device)
-        _WS[key] = t
-    return t
-
-
-# -----------------------------------------------------------------------------------------------------
-# deferred leaf reductions (mvk_defer_begin, include/mvk.h)
-# -----------------------------------------------------------------------------------------------------
-# Weight / bias gradients are leaves: between `deferred_reductions(flat)` and its exit the ordered finishes of every
-# gradient that accumulates into the flat buffer (split-K slabs, column-sum partials, convolution weight-gradient slabs)
-# are queued and run in ONE launch at exit instead of one small launch each in the middle of the backward chain.
-DEFER = _lib.tune("MVK_DEFER", "1") != "0"
-# The arena starts at 64 MB and grows between steps to what the last step asked for (mvk_defer_wanted), up to MVK_DEFER_MB
-# (default 1024): an MLP model keeps 64 MB, the MnistSvhn models settle at ~200 MB, the ResNet configurations at the cap
-# (ADVICE r2: a fixed 512 MB per device was wasteful for small models and too small for cfg5).  Grown only outside a stream
-# capture; a replaced arena stays alive (a captured graph may hold its address).
-DEFER_ARENA_CAP_FLOATS = int(os.environ.get("MVK_DEFER_MB", "1024")) * (1 << 18)
-DEFER_ARENA_START_FLOATS = min(64 * (1 << 18), DEFER_ARENA_CAP_FLOATS)
-_ARENA = {}
-_ARENA_RETIRED = []
-_ARENA_CAPTURED = set()  # data_ptr of every arena that was live during a stream capture
-
-
-_DEFER_ACTIVE = set()  # devices inside deferred_reductions
-_LATE_USED = {}  # device -> streams that hold late leaves / partial flushes since mvk_defer_begin (joined at its end)
-# MVK_LATE_LEAVES=1: the weight gradients of the large decoder (two ~100 us launches that fill the chip) are enqueued AFTER
-# its backward-data chain, on a stream that is joined only where the deferred finishes run: they execute beside the
-# launch-latency-bound encoder backward (the ~300 us tail of the step in which the chip is mostly idle) instead of in
-# front of it.
-# MEASURED (headline step, same box, two pairs): 1.347 / 1.336 ms without vs 1.320 / 1.315 ms with; a smaller grid for the
-# weight-gradient kernels (MVK_IMGWGRAD_GRID=224 / 192 / 128: compute units left free for the chain) does not help
-# (1.331 / 1.348 / 1.414 ms).  MVK_LATE_LEAVES=0 disables.
-LATE_LEAVES = _lib.tune("MVK_LATE_LEAVES", "1") != "0"
-
-
-class late_leaves:
-    """with late_leaves(device, *tensors_read): the enclosed launches go to the late-leaf stream, ordered behind what the
-    current stream holds now; nothing waits for them until deferred_reductions ends.  Outside deferred_reductions (or with
-    MVK_LATE_LEAVES=0, or on the CPU) the launches stay on the current stream."""
-
-    def __init__(self, device, *reads):
-        self.on = LATE_LEAVES and device.type == "cuda" and device in _DEFER_ACTIVE
-        self.device, self.reads, self._ctx = device, reads, None
-
-    def __enter__(self):
-        if self.on:
-            st = _side_stream(self.device, 30)
-            st.wait_event(torch.cuda.current_stream(self.device).record_event())
-            for t in self.reads:
-                t.record_stream(st)
-            _LATE_USED.setdefault(self.device, []).append(st)
-            self._ctx = torch.cuda.stream(st)
-            self._ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self._ctx is not None:
-            self._ctx.__exit__(*exc)
-            self._ctx = None
-        return False
-
-
-_LATE_CALLS = {}  # device -> closures run on the late-leaf stream when deferred_reductions ends (behind every other late leaf)
-# Of the MLP decoder's weight gradients only the first layer's (a split-K launch of 16 us alone, 50-60 us beside the convolutions)
-# is postponed: autograd orders the posterior's backward behind EVERYTHING the decoder's backward node enqueued on its stream,
-# leaves included.  MEASURED (three same-box pairs): 1.046 / 1.050 / 1.039 -> 1.042 / 1.040 / 1.032 ms.  Postponing ALL of them
-# lost (1.099 / 1.093 / 1.094 ms without vs 1.114 / 1.104 / 1.106 ms with: the tail — the encoders' backward, a dependent chain of
-# small kernels — slows down by what the decoder window gains).
-
-
-def run_last(device, fn, *reads, params=()):
-    """Inside deferred_reductions: run fn() on the late-leaf stream AFTER everything else the backward pass puts there (the
-    enqueue itself is postponed to the end of the scope), i.e. in the launch-latency-bound tail of the step where the chip is
-    mostly idle, instead of beside the decoders' backward-data chains whose window is throughput-bound.  Returns False when
-    there is no such scope (the caller runs fn itself)."""
-    if not LATE_LEAVES or device.type != "cuda" or device not in _DEFER_ACTIVE:
-        return False
-    _LATE_CALLS.setdefault(device, []).append((fn, reads))
-    op = _OVERLAP.get(device)
-    if op is not None:  # these gradients are written in the tail of the step: not part of the early collective
-        op.late_params.extend(params)
-    return True
-
-
-# -----------------------------------------------------------------------------------------------------
-# where the backward pass says "this part of the gradient buffer is final" (overlapped data-parallel collective)
-# -----------------------------------------------------------------------------------------------------
-_OVERLAP = {}  # device -> OverlapPoint, while trainers.graph enqueues / captures a data-parallel step
-
-
-class OverlapPoint:
-    """The reference's DDP reduces gradient buckets while loss.backward() still runs (trainers/base/base_trainer.py:116-117,359).
-    Here the step is ONE replayed hipGraph, so the overlap needs a point INSIDE the graph that a stream OUTSIDE can wait for: an
-    external event-record node (mvk_event_record(ev, 1, stream)), placed where the finishes of everything but the last backward
-    node have run (defer_flush_sibling: the decoders', the posterior's and the short encoder's gradients are final there, the
-    long encoder's backward chain — ~300 us of the headline step — is still ahead).  `late_params` collects the parameters whose
-    gradients are NOT final at that point: the node that called defer_flush_sibling and every leaf postponed by run_last."""
-
-    def __init__(self, device):
-        self.device = device
-        self.event = C.c_void_p()
-        call("mvk_event_create", C.byref(self.event))
-        self.late_params = []
-        self.recorded = False
-
-    def begin(self):
-        self.late_params, self.recorded = [], False
-        _OVERLAP[self.device] = self
-
-    def end(self):
-        _OVERLAP.pop(self.device, None)
-
-    def __del__(self):
-        try:
-            if self.event:
-                _lib.load().mvk_event_destroy(self.event)
-        except Exception:
-            pass
-
-
-# -----------------------------------------------------------------------------------------------------
-# the rotated step: leaf gradients of step N at the head of step N + 1 (trainers/graph.py GraphedStep(rotate=True))
-# -----------------------------------------------------------------------------------------------------
-# The reference's loop is strictly sequential (trainers/base/base_trainer.py:350-361: zero_grad, forward, backward, step), but
-# nothing in its semantics ties a DECODER's weight gradients and their share of optimizer.step() of step N to anything before
-# that decoder's forward pass of step N + 1.  In a rotated step the decoders' weight-gradient launches (leaves of the backward
-# pass: nothing waits for them) are not enqueued by the backward pass; their closures are kept and run at the head of the
-# next step on a branch of their own — beside the encoders' forward pass and the posterior, the launch-latency-bound head of
-# the step in which the chip is mostly idle — followed by their ordered finishes, the Adam update of exactly those
-# parameters (mvk_adam_step_dev with the scalars the step's main update published: mvk_adam_step_pub) and the weight packs
-# that read them; the decoders' forward pass waits for that branch.  Every parameter is updated once per step, with the same
-# gradient and the same scalars, before it is next read: the parameters after N steps + a drain are bit for bit those of N
-# unrotated steps (tests/test_gpu_trainer.py).  What a leaf reads must survive into the next replay at a fixed address:
-# `Rotation.buf` hands out persistent buffers, `Rotation.slots` persistent amax slots (zeroed by the branch behind the leaves).
-# MVK_ROT_SVHN / MVK_ROT_MLP: 0 = that decoder's leaves stay in the step they belong to; 1 = all of its weight-gradient leaves are
-# rotated (the large, register-stationary launches too); 2 = only its FIRST layer's (a split-K GEMM of 10-25 us whose workgroups
-# fit beside anything: the kind of launch the head of the step has room for).
-ROT_SVHN = int(_lib.tune("MVK_ROT_SVHN", "1"))
-ROT_MLP = int(_lib.tune("MVK_ROT_MLP", "1"))
-_ROTATE = {}  # device -> Rotation, while trainers.graph enqueues / captures a rotated step
-
-
-def rotation(device):
-    """The open Rotation of a device, or None."""
-    return _ROTATE.get(device) if _ROTATE else None
-
-
-class Rotation:
-    def __init__(self, device):
-        self.device = device
-        self.bufs = {}
-        self.amax = torch.zeros(64, dtype=torch.float32, device=device)
-        self.amax_pos = 0
-        self.leaves = []    # registered by the backward pass that is being enqueued: (closure, parameters, prepare)
-        self.pending = []   # those of the previous pass: what the head of the next one runs
-        self.cache = {}     # pack key -> what the head's `prepare` closures packed BEHIND the update of the rotated parameters
-        self.event = None
-        self.waited = set()
-        self.stream = _side_stream(device, 29)
-        self.open = False
-
-    def buf(self, name, shape, dtype=torch.float32):
-        """A buffer that keeps its address from pass to pass (and from replay to replay)."""
-        t = self.bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
-            if t is not None and torch.cuda.is_current_stream_capturing():
-                raise _lib.MvkError(f"rotated step: buffer {name} changes shape inside a capture")
-            t = torch.zeros(tuple(shape), dtype=dtype, device=self.device)
-            self.bufs[name] = t
-        return t
-
-    def slots(self, n):
-        """n amax slots that are zero now and stay untouched until the head of the next step has run its leaves."""
-        if self.amax_pos + n > self.amax.numel():
-            raise _lib.MvkError("rotated step: out of amax slots")
-        self.amax_pos += n
-        return self.amax[self.amax_pos - n:self.amax_pos]
-
-    @property
-    def params(self):
-        """The parameters whose gradients (and update) are rotated, in registration order."""
-        out, seen = [], set()
-        for _, ps, _ in self.pending:
-            for q in ps:
-                if id(q) not in seen:
-                    seen.add(id(q))
-                    out.append(q)
-        return out
-
-    def push(self, fn, params, prepare=None):
-        self.leaves.append((fn, tuple(params), prepare))
-
-    def begin_step(self, update=None):
-        """Inside deferred_reductions, at the head of the forward pass: the branch of the previous step's leaves.  update: the
-        closure that applies the optimizer to the rotated parameters (captured passes only; eager warm-up passes leave the
-        parameters alone)."""
-        cur = torch.cuda.current_stream(self.device)
-        st = self.stream
-        st.wait_event(cur.record_event())
-        self.cache, self.waited, self.open = {}, set(), True
-        with torch.cuda.stream(st):
-            for fn, _, _ in self.pending:
-                fn()
-            if self.pending:
-                call("mvk_defer_flush", stream_ptr())  # their ordered finishes: the gradients of the rotated parameters are final
-                if update is not None:
-                    update()
-            self.amax.zero_()  # the slots the leaves read are free for this step's producers
-            self.amax_pos = 0
-            for _, _, prepare in self.pending:
-                if prepare is not None:
-                    prepare(self)
-            self.event = st.record_event()
-        self.leaves = []
-        _ROTATE[self.device] = self
-
-    def wait(self):
-        """Order the current stream behind the head branch (whoever reads a rotated parameter, or a pack of one, calls this)."""
-        if not self.open or self.event is None:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur.cuda_stream not in self.waited:
-            cur.wait_event(self.event)
-            self.waited.add(cur.cuda_stream)
-            for t in _tensors_of(list(self.cache.values())):  # allocated on the branch's stream, read on this one
-                t.record_stream(cur)
-                if getattr(t, "mvk_frag", None) is not None:
-                    t.mvk_frag.record_stream(cur)
-
-    def end_step(self):
-        """Behind the backward pass: the branch is joined (it is, transitively, when a decoder waited for it), the leaves the
-        backward pass registered become the next head's."""
-        _ROTATE.pop(self.device, None)
-        if self.open:
-            self.wait()
-            self.open = False
-        self.pending, self.leaves = self.leaves, []
-
-    def run_pending(self):
-        """The drain: the pending leaves on the current stream (inside deferred_reductions), no update, no packs."""
-        for fn, _, _ in self.pending:
-            fn()
-
-
-_LATE_READY = {}
-
-
-def late_ready(device):
-    """Called on the main stream where every decoder's backward has been joined (the posterior's backward): the postponed
-    leaves of run_last may start behind this point."""
-    if device in _LATE_CALLS:
-        _LATE_READY[device] = torch.cuda.current_stream(device).record_event()
-
-
-_LOSS_EVENT = {}  # device -> event behind the loss assembly when it ran on the late-leaf stream (ReconLossFn, async_ok)
-# MVK_ASYNC_LOSS=0: the loss assembly stays on the caller's stream, between the last forward and the first backward launch
-ASYNC_LOSS = _lib.tune("MVK_ASYNC_LOSS", "1") != "0"
-
-
-def orders_behind_loss(rows):
-    """True when the backward node that produced `rows` (a fused decoder tail's NLL row sums) is one of this package's, i.e.
-    known to call wait_loss before it reads a row gradient the assembly launch fills.  A user decoder may implement
-    `reconstruction_nll` with ordinary autograd ops: its backward would read the row-gradient buffer with NO ordering against an
-    assembly launch on the late-leaf stream — in a captured graph a missing dependency, silently wrong gradients.
-    Models set spec["async_ok"] only when this holds for every fused term."""
-    fn = getattr(rows, "grad_fn", None)
-    if fn is None:
-        return not getattr(rows, "requires_grad", False)
-    return isinstance(fn, (MLPDecoderFn._backward_cls, SVHNDecoderFn._backward_cls))
-
-
-_LOSS_POSTPONED = {}  # device -> the assembly launch as a closure, while it waits among the postponed leaves (ReconLossFn, assembly_last)
-# MVK_ASSEMBLY_LAST=0: the assembly launch at the head of the backward pass on the late-leaf stream (the round-5 place; A/B)
-ASSEMBLY_LAST = _lib.tune("MVK_ASSEMBLY_LAST", "1") != "0"
-
-
-def wait_loss(device):
-    """Order the current stream behind the loss assembly launch.  Every backward node that READS a gradient buffer the assembly
-    fills (the KL rows' gradients, a fused tail's row gradients on its general path) calls this first; nodes that take the
-    constant from `const_grad` do not wait for anything.  An assembly that was postponed to the end of the step (nobody was
-    expected to read what it fills) runs HERE, on the caller's stream, when somebody does."""
-    fn = _LOSS_POSTPONED.pop(device, None)
-    if fn is not None:
-        calls = _LATE_CALLS.get(device, [])
-        calls[:] = [c for c in calls if c[0] is not fn]
-        fn()
-        return
-    ev = _LOSS_EVENT.get(device)
-    if ev is not None:
-        torch.cuda.current_stream(device).wait_event(ev)
-
-
-_CONST_ROWS = {}  # (device, n, value) -> a tensor of n floats holding `value` (made in an eager pass, kept: captured graphs read it)
-
-
-def const_rows(device, n, value):
-    key = (device, int(n), float(value))
-    t = _CONST_ROWS.get(key)
-    if t is None:
-        if torch.cuda.is_current_stream_capturing():
-            return None  # never allocate a cached buffer inside a capture (it would live in that graph's pool)
-        t = torch.full((int(n),), float(value), dtype=torch.float32, device=device)
-        _CONST_ROWS[key] = t
-    return t
-
-
-class deferred_reductions:
-    """with deferred_reductions(flat): forward + backward.  On exit the queued finishes run on the current stream; the
-    gradient buffer is complete after that (before: NOT).  A no-op on CPU tensors or with MVK_DEFER=0."""
-
-    def __init__(self, flat):
-        g = getattr(flat, "grad", None)
-        self.on = DEFER and g is not None and g.is_cuda and g.numel() > 0
-        self.grad = g
-
-    def __enter__(self):
-        if self.on:
-            dev = self.grad.device
-            arena = _ARENA.get(dev)
-            if arena is None:
-                arena = torch.empty(DEFER_ARENA_START_FLOATS, dtype=torch.float32, device=dev)
-                _ARENA[dev] = arena
-            if torch.cuda.is_current_stream_capturing():
-                _ARENA_CAPTURED.add(arena.data_ptr())  # a hipGraph holds pointers into it: it must outlive the graph
-            call("mvk_defer_begin", ptr(arena), arena.numel(), ptr(self.grad), self.grad.numel())
-            _DEFER_ACTIVE.add(dev)
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if self.on:
-            dev = self.grad.device
-            late = _LATE_CALLS.pop(dev, ())
-            if late:  # postponed leaves: enqueued now, on the late-leaf stream, behind the other late leaves
-                # Ordered behind a MAIN-stream event (late_ready: recorded where the posterior's backward starts, i.e. behind the
-                # join of every decoder's backward), never behind the producer's branch stream itself: the partial flush on a branch
-                # stream waits for the late-leaf stream, a late-leaf stream that waited for that branch stream made the two
-                # "parallel capture streams" of each other and hip::Stream::EndCapture recursed until the stack overflowed; a
-                # stream of its own changed the queue assignment of the replayed graph (the encoders' backward chain landed
-                # behind the postponed launches: 1.10 -> 1.19 ms).
-                st = _side_stream(dev, 30)
-                ev = _LATE_READY.pop(dev, None)
-                st.wait_event(ev if ev is not None else torch.cuda.current_stream(dev).record_event())
-                _LATE_USED.setdefault(dev, []).append(st)
-                with torch.cuda.stream(st):
-                    for fn, reads in late:
-                        for t in reads:
-                            t.record_stream(st)
-                        fn()
-            _DEFER_ACTIVE.discard(dev)
-            _LATE_READY.pop(dev, None)
-            _LOSS_EVENT.pop(dev, None)  # the late-leaf stream is joined below
-            _LOSS_POSTPONED.pop(dev, None)
-            _BIG_LATE.discard(dev)
-            cur = torch.cuda.current_stream(dev)
-            for st in dict.fromkeys(_LATE_USED.pop(dev, ())):  # the late leaves (below) and sibling flushes end here
-                if st != cur:
-                    cur.wait_stream(st)
-            call("mvk_defer_end", stream_ptr())
-            wanted = int(_lib.load().mvk_defer_wanted())
-            arena = _ARENA[dev]
-            if wanted > arena.numel() and arena.numel() < DEFER_ARENA_CAP_FLOATS and not torch.cuda.is_current_stream_capturing():
-                if arena.data_ptr() in _ARENA_CAPTURED:  # only an arena a captured graph points into is kept alive
-                    _ARENA_RETIRED.append(arena)
-                else:
-                    arena.record_stream(cur)  # the finish launch above still reads it: no reuse before that has run
-                grown = 1 << (wanted + wanted // 8 - 1).bit_length()  # powers of two: a creeping demand grows it log(n) times
-                _ARENA[dev] = torch.empty(min(DEFER_ARENA_CAP_FLOATS, grown), dtype=torch.float32, device=dev)
-        return False
-
-
-# When the LAST backward node of the step starts (the convolutional encoder: ~140 us of launch-latency-bound
-# chain on its own stream), everything queued so far is finished on the other branch stream, which is idle by then, instead of
-# in one launch behind the chain.
-_BRANCH_SET = {}  # device -> the streams of the last run_branches call (main first)
-
-
-def defer_flush_sibling(device, node_params=()):
-    """node_params: the parameters of the backward node that calls this (the LAST one of the step): with an OverlapPoint open,
-    everything else's gradient is final behind the flush, and the point is recorded there."""
-    if not DEFER or device.type != "cuda" or device not in _DEFER_ACTIVE:
-        return
-    cur = torch.cuda.current_stream(device)
-    sib = next((st for st in _BRANCH_SET.get(device, ()) if st != cur), None)
-    if sib is None or _lib.load().mvk_defer_pending() == 0:
-        return
-    with torch.cuda.stream(sib):
-        call("mvk_defer_flush", stream_ptr())
-        op = _OVERLAP.get(device)
-        if op is not None and not op.recorded:
-            # the flush already waits for every stream a gradient producer RAN ON (csrc/igemm.hip defer_flush_locked); ordered
-            # explicitly behind the caller's stream and the late-leaf streams as well: a gradient written straight into the
-            # buffer by a launch that queued no finish would otherwise be unordered against the collective
-            # (ADVICE r5: ... and behind EVERY branch stream of the step, not only the caller's: a backward node of another branch
-            # that is enqueued already must have written its gradients before the collective reads them)
-            for st in dict.fromkeys([cur] + list(_BRANCH_SET.get(device, ())) + list(_LATE_USED.get(device, ()))):
-                if st != sib:
-                    sib.wait_event(st.record_event())
-            call("mvk_event_record", op.event, 1, stream_ptr())
-            op.late_params.extend(node_params)
-            op.recorded = True  # from here on every gradient target handed out is late (_grad_target): whatever node asks
-    _LATE_USED.setdefault(device, []).append(sib)
-
-
-# -----------------------------------------------------------------------------------------------------
-# modality branches on separate HIP streams
-# -----------------------------------------------------------------------------------------------------
-# The encoders (and the decoders) of different modalities are independent until the posterior (resp. the
-# reconstruction loss) joins them.  The small-modality branch is a string of short, launch-latency-bound
-# kernels; on its own stream it runs beside the large modality's convolutions instead of in front of them.
-# Autograd replays each node's backward on the stream its forward ran on, so the backward overlaps too.
-BRANCH_STREAMS = _lib.tune("MVK_BRANCH_STREAMS", "1") != "0"
-_SIDE = {}
-
-
-def _side_stream(device, i):
-    key = (device, i)
-    st = _SIDE.get(key)
-    if st is None:
-        # default priority: a priority -1 side stream costs +75 % step time (1.38 -> 2.4 ms, measured in round 2)
-        st = _lib.new_stream(device)  # dedicated: never one of torch's 32 pooled streams (see _lib.new_stream)
-        _SIDE[key] = st
-    return st
-
-
-def _tensors_of(obj):
-    if torch.is_tensor(obj):
-        yield obj
-    elif isinstance(obj, dict):
-        for v in obj.values():
-            yield from _tensors_of(v)
-    elif isinstance(obj, (list, tuple)):
-        for v in obj:
-            yield from _tensors_of(v)
-
-
 # MVK_WGRAD_PAIR=0: the convolutional encoder's two inner weight gradients as two launches inside the backward-data chain (A/B)
 WGRAD_PAIR = _lib.tune("MVK_WGRAD_PAIR", "1") != "0"
-
-
-# The decoders' side branches are CREATED before the main one (run_branches(side_first=True)), so that autograd enqueues the main
-# branch's backward first and a side branch's backward can be ordered behind the main branch's HBM-bound tail kernel
-# (tail_bwd_done / wait_tail_bwd).  Two memory-heavy launches that share the chip are slower than the same two in a row:
-# small_up_bwd_bf_kernel took 139 us beside the MLP decoder's backward-data GEMM (95 us), 82 and 32 us alone.  MEASURED (three
-# same-box pairs): 1.087 / 1.080 / 1.095 ms -> 1.040 / 1.055 / 1.050 ms.
-_TAIL_EVENT = {}
-
-
-def tail_bwd_done(device):
-    """SVHNDecoderFn.backward, right behind its image-layer launch."""
-    if device in _DEFER_ACTIVE:
-        _TAIL_EVENT[device] = torch.cuda.current_stream(device).record_event()
-
-
-def wait_tail_bwd(device):
-    """A side branch's decoder backward: start behind the main branch's tail kernel when that one was enqueued first."""
-    ev = _TAIL_EVENT.pop(device, None)
-    if ev is not None:
-        torch.cuda.current_stream(device).wait_event(ev)
-
-
-_PRELUDE = {}  # device -> closure with launches that depend on nothing of the step (run at the head of the first side branch)
-
-
-def set_prelude(device, fn):
-    """Launches that the step needs LATER and that depend on nothing it computes (the optimizer's scalar preparation inside a
-    captured step): enqueued at the head of the first side branch run_branches opens — a stream with slack, joined long before
-    the optimizer — instead of on the critical chain.  run_prelude(device) runs it where it is if no branch took it."""
-    _PRELUDE[device] = fn
-
-
-def run_prelude(device):
-    fn = _PRELUDE.pop(device, None)
-    if fn is not None:
-        fn()
-
-
-def run_branches(names, fn, device, side_first=False):
-    """{m: fn(m)} with every branch but the first on its own stream; joined before returning."""
-    names = list(names)
-    if not BRANCH_STREAMS or len(names) < 2 or device.type != "cuda":
-        return {m: fn(m) for m in names}
-    main = torch.cuda.current_stream(device)
-    _BRANCH_SET[device] = [main] + [_side_stream(device, i) for i in range(1, len(names))]
-    fork = main.record_event()
-    # The first branch stays on the caller's stream and is enqueued FIRST: autograd runs backward nodes in reverse
-    # creation order, so the side branches' backward is enqueued (and, in a captured graph, ordered) before the long
-    # backward of the main branch instead of behind it.
-    outs = {}
-    if not side_first:
-        outs[names[0]] = fn(names[0])
-    sides = []
-    for i, m in enumerate(names[1:], start=1):
-        st = _side_stream(device, i)
-        st.wait_event(fork)
-        sides.append(st)
-        with torch.cuda.stream(st):
-            run_prelude(device)
-            outs[m] = fn(m)
-        for t in _tensors_of(outs[m]):
-            t.record_stream(main)
-    if side_first:
-        outs[names[0]] = fn(names[0])
-    for st in sides:
-        main.wait_stream(st)
-    return {m: outs[m] for m in names}
 
 
 # =====================================================================================================
@@ -608,8 +104,9 @@ def _grad_target(p):
     and autograd gets None for this input (no zero-fill, no extra add kernel); otherwise a fresh zero buffer is
     returned to autograd as usual.  Both ways the visible semantics are `p.grad += dL/dp`."""
     g = p.grad
-    if _OVERLAP:
-        op = _OVERLAP.get(p.device)
+    sc = schedule.scope(p.device)
+    if sc is not None:
+        op = sc.overlap
         if op is not None and op.recorded:
             # ADVICE r5: a gradient produced behind the overlap point — by the node that recorded it or by ANY node enqueued
             # later (a second SVHN-type encoder, an encoder on a side branch) — is not part of the early collective
@@ -674,20 +171,15 @@ HEADS_BWD = _lib.tune("MVK_HEADS_BWD", "1") != "0"  # A/B switch: the heads' bac
 # workgroups with 48-62 KB of LDS wait for room beside those leaves) — while WITHOUT such leaves (decoder batch < 1024 rows:
 # MMVAE MnistSvhn 0.516 / 0.533 fused against 0.560 / 0.559, MoPoE at K = 1 0.509 / 0.521 against 0.537 / 0.540) the fused launch
 # wins by 5-8 %.  "auto" (default): fused unless a backward node of this scope enqueued register-stationary late leaves
-# (big_late_leaves); MVK_HEADS_BWD_MLP=0 / 1 force one form.
+# (schedule.big_late_leaves); MVK_HEADS_BWD_MLP=0 / 1 force one form.
 _HEADS_BWD_MLP_MODE = _lib.tune("MVK_HEADS_BWD_MLP", "auto")
-_BIG_LATE = set()  # devices on which a backward node of the open deferred_reductions scope enqueued register-stationary late leaves
-
-
-def big_late_leaves(device):
-    _BIG_LATE.add(device)
 
 
 def heads_bwd_mlp(device):
     """Whether an MLP encoder's heads take the one-launch backward now."""
     if _HEADS_BWD_MLP_MODE in ("0", "1"):
         return _HEADS_BWD_MLP_MODE == "1"
-    return device not in _BIG_LATE
+    return not schedule.has_big_late_leaves(device)
 
 
 def heads_bwd(x, x_act, dys, ws_, bs, w_sk, w_sn, flat_c=0, want_dx=True, prev_bias=None, dw_params=None):
@@ -784,7 +276,7 @@ def pack_weights(jobs):
     """`_pack_launch(jobs)`, or inside a pack_scope: from the scope's cache / together with every announced job of the model."""
     sc = _PACK_SCOPE
     keys = [_job_key(j) for j in jobs]
-    rot = rotation(jobs[0][0].device)
+    rot = schedule.rotation(jobs[0][0].device)
     if rot is not None and rot.cache:  # some (or all) of them packed by the head branch of a rotated step, behind their update
         hit = [k in rot.cache for k in keys]
         if any(hit):
@@ -1111,7 +603,6 @@ def upsample2_bwd(dy, n, H, W, C):
 # ---- noise with the generator state in device memory (mvk_device_rng) -------------------------------------------------
 # MVK_DEVICE_RNG=0: draw from torch's generator instead (two extra host-issued fill launches per hipGraph replay).
 DEVICE_RNG = _lib.tune("MVK_DEVICE_RNG", "1") != "0"
-_RNG = {}  # device -> [state tensor (3 x int64: seed, offset, ticket), torch seed it was built from, breadcrumb offset]
 
 
 def _rng_state(device):
@@ -1383,7 +874,7 @@ def dense16_pack(w, raw=False):
     pack_scope (the cache dies with the scope: the weights change at the next optimizer step).  raw: launch here, no cache."""
     sc = _PACK_SCOPE
     key = ("dense16", w.data_ptr(), tuple(w.shape))
-    rot = rotation(w.device)
+    rot = schedule.rotation(w.device)
     if not raw and rot is not None and key in rot.cache:  # packed by the head branch of a rotated step, behind w's update
         rot.wait()
         return rot.cache[key]
@@ -1410,9 +901,6 @@ def dense16_xamax(x):
     if sc is not None:
         sc["cache"][key] = slot
     return slot
-
-
-_CONST_GRADS = {}  # data_ptr -> (weakref of the tensor, numel, value): gradient buffers known to hold ONE constant
 
 
 def register_const_grad(t, value):
@@ -1454,6 +942,8 @@ class MLPDecoderFn(Function):
     are expected to enter the loss with (d loss / d rows): when the backward pass receives exactly that constant (const_grad)
     nothing is rescaled; any other upstream gradient takes the general path (planes -> fp32 times the row factor)."""
 
+    WAITS_FOR_LOSS = True  # the backward calls schedule.wait_loss before it reads a row gradient (schedule.orders_behind_loss)
+
     @staticmethod
     def forward(ctx, z, w0, b0, w1, b1, input_dim, nll_x=None, nll_scale=1.0, nll_weight=1.0):
         _check_nll_weight(nll_x, nll_weight)
@@ -1465,18 +955,18 @@ class MLPDecoderFn(Function):
             n, H, D = z2.shape[0], w0.shape[0], w1.shape[0]
             # rotated step (Rotation): the weight gradients of w1 / b1 / w0 run at the head of the NEXT step; what they read (z,
             # the planes of h and of the stored gradient, their bounds, the column-sum partials; dh in backward) is persistent
-            rot = rotation(z2.device)
+            rot = schedule.rotation(z2.device)
             if rot is not None:
                 rot.wait()  # w0 is read as it is, w1 through planes packed behind its update
-            if not (ROT_MLP and rot is not None and LATE_LEAVES and z2.device in _DEFER_ACTIVE
+            if not (schedule.ROT_MLP and rot is not None and schedule.LATE_LEAVES and schedule.scope(z2.device) is not None
                     and all(_is_direct(t) for t in (w0, w1, b1))):
                 rot = None
-            ctx.rot, ctx.rot_mode = rot, ROT_MLP
-            if rot is not None and ROT_MLP == 2:
+            ctx.rot, ctx.rot_mode = rot, schedule.ROT_MLP
+            if rot is not None and schedule.ROT_MLP == 2:
                 # mode 2 rotates the first layer's gradient only: z at a fixed address (copied HERE, on this branch's stream: the
                 # late-leaf stream must never wait for a branch stream — hip::Stream::EndCapture recursion, see deferred_reductions)
                 z2 = rot.buf(("mlp_dec", w0.data_ptr(), z2.shape[0], "z"), z2.shape).copy_(z2)
-            if ROT_MLP != 1:
+            if schedule.ROT_MLP != 1:
                 rot = None
             rkey = ("mlp_dec", w0.data_ptr(), n)
             nk, nk_inv, kn, kn_inv = dense16_pack(w1)
@@ -1542,7 +1032,7 @@ class MLPDecoderFn(Function):
     @staticmethod
     def _backward_fused(ctx, drows):
         z2, hp, gp, bounds, kn, kn_inv, cs, w0, b0, w1, b1 = ctx.saved_tensors
-        wait_tail_bwd(z2.device)
+        schedule.wait_tail_bwd(z2.device)
         n, H, D = z2.shape[0], w0.shape[0], w1.shape[0]
         hb, gb = bounds[0:1], bounds[1:2]
         c = const_grad(drows)
@@ -1552,7 +1042,7 @@ class MLPDecoderFn(Function):
             tw1, dw1 = _grad_target(w1)
             tb1, db1 = _grad_target(b1)
             tb0, db0 = _grad_target(b0)
-            rot = ctx.rot if (ctx.rot is not None and rotation(z2.device) is ctx.rot and dw1 is None and db1 is None) else None
+            rot = ctx.rot if (ctx.rot is not None and schedule.rotation(z2.device) is ctx.rot and dw1 is None and db1 is None) else None
             rot0 = rot if (rot is not None and ctx.rot_mode == 2) else None
             dh = _new((n, H), z2) if rot is None else rot.buf(("mlp_dec", w0.data_ptr(), n, "dh"), (n, H))
             if rot0 is not None:
@@ -1586,11 +1076,11 @@ class MLPDecoderFn(Function):
             dw0 = None
             if rot0 is not None:  # mode 2: the first layer's weight gradient is the head of the next step (z2 is the fixed copy)
                 rot0.push(lambda: linear_bwd_weight(dh, z2, w0, None), (w0,), None)
-            elif not _is_direct(w0) or not run_last(z2.device, lambda: linear_bwd_weight(dh, z2, w0, None), dh, z2, params=(w0,)):
+            elif not _is_direct(w0) or not schedule.run_last(z2.device, lambda: linear_bwd_weight(dh, z2, w0, None), dh, z2, params=(w0,)):
                 dw0, _ = linear_bwd_weight(dh, z2, w0, None)
             return dz, dw0, db0, dw1, db1, None, None, None, None
         else:  # general upstream gradient: d pre = G * drows[column tile, row] / nll_weight as an fp32 tensor, then the tiled engine
-            wait_loss(z2.device)
+            schedule.wait_loss(z2.device)
             drows = _c(drows).reshape(-1, n)
             dpre = _new((n, D), z2)
             h = _new((n, H), z2)
@@ -1656,7 +1146,7 @@ class SVHNEncoderFn(Function):
         dmu, dlv = _c(dmu).view(B, L), _c(dlv).view(B, L)
         Kf = 16 * ch[3]
         h3f = h3.view(B, Kf)
-        defer_flush_sibling(x.device, node_params=(w0, b0, w1, b1, w2, b2, wc1, bc1, wc2, bc2))
+        schedule.defer_flush_sibling(x.device, node_params=(w0, b0, w1, b1, w2, b2, wc1, bc1, wc2, bc2))
         # heads: both weight gradients (in the Conv2d layout), both bias gradients, d h3 (pre-activation: dmu Wd1^T + dlv Wd2^T
         # with ReLU'(h3)) and its channel sums (the bias gradient of the layer below) in one launch
         fused = heads_bwd(h3f, RELU, [dmu, dlv], [wdc1, wdc2], [bc1, bc2], L, 1, flat_c=ch[3], prev_bias=b2,
@@ -1677,7 +1167,7 @@ class SVHNEncoderFn(Function):
         # training batch each is a split-K GEMM of 256 workgroups and ~35 us, and the four launches were one dependent chain
         # (the step's last one).  Only where both targets are views of the flat gradient buffer inside deferred_reductions (the
         # pair's slabs live in the arena).
-        pair = (WGRAD_PAIR and x.device in _DEFER_ACTIVE and _is_direct(w1) and _is_direct(w2)
+        pair = (WGRAD_PAIR and schedule.scope(x.device) is not None and _is_direct(w1) and _is_direct(w2)
                 and x.device.type == "cuda")
         if not pair:
             dw2 = conv_wgrad(h2, dh3, w2, B, H // 8, W // 8, ch[2], ch[3])
@@ -1715,6 +1205,8 @@ TAIL_BWD_F16 = _lib.tune("MVK_TAIL_BWD_F16", "1") != "0"
 class SVHNDecoderFn(Function):
     """z[...,L] -> ConvT(4,1,0)+ReLU -> 2x ConvT(4,2,1)+ReLU -> ConvT(4,2,1)+Sigmoid -> [...,C,32,32] NCHW."""
 
+    WAITS_FOR_LOSS = True  # the backward calls schedule.wait_loss before it reads a row gradient (schedule.orders_behind_loss)
+
     @staticmethod
     def forward(ctx, z, w0, b0, w1, b1, w2, b2, w3, b3, nll_x=None, nll_scale=1.0, nll_weight=1.0):
         """nll_x [B, C, 32, 32] given: the FUSED TAIL — the last layer scores its image against nll_x[row % B] by a
@@ -1738,14 +1230,14 @@ class SVHNDecoderFn(Function):
         ctx.f16 = f16
         # rotated step (Rotation): the three weight gradients of w0 / w1 / w2 run at the head of the NEXT step — what they read
         # (z, g1, g2 here; the three gradients in backward; the amax slots) lives in the rotation's persistent buffers
-        rot = rotation(z2.device)
+        rot = schedule.rotation(z2.device)
         if rot is not None:
             rot.wait()  # w0 / w1 / w2 (and their packs above) are final behind the head branch
-        if not (ROT_SVHN and rot is not None and f16 and nll_x is not None and LATE_LEAVES and z2.device in _DEFER_ACTIVE
-                and all(_is_direct(t) for t in (w0, w1, w2))):
+        if not (schedule.ROT_SVHN and rot is not None and f16 and nll_x is not None and schedule.LATE_LEAVES
+                and schedule.scope(z2.device) is not None and all(_is_direct(t) for t in (w0, w1, w2))):
             rot = None
-        ctx.rot, ctx.rot_mode = rot, ROT_SVHN
-        if ROT_SVHN != 1:
+        ctx.rot, ctx.rot_mode = rot, schedule.ROT_SVHN
+        if schedule.ROT_SVHN != 1:
             rot = None  # mode 2 rotates the first layer's gradient only: nothing of the forward pass needs a fixed address
         rkey = ("svhn_dec", w0.data_ptr(), n)
         if rot is not None:
@@ -1819,13 +1311,13 @@ class SVHNDecoderFn(Function):
             if c is not None and c == ctx.nll_weight:
                 drows = None  # exactly the weight folded into `out`: no row gradient is read (nor waited for)
             else:
-                wait_loss(dout.device)
+                schedule.wait_loss(dout.device)
                 drows = _c(dout).reshape(-1)
                 if ctx.nll_weight != 1.0:
                     drows = drows * (1.0 / ctx.nll_weight)
             tw3, dw3 = _grad_target(w3)
             tb3, db3 = _grad_target(b3)
-            rot = ctx.rot if (ctx.rot is not None and ctx.rot_mode == 1 and rotation(z2.device) is ctx.rot) else None
+            rot = ctx.rot if (ctx.rot is not None and ctx.rot_mode == 1 and schedule.rotation(z2.device) is ctx.rot) else None
             rkey = ("svhn_dec", w0.data_ptr(), n)
             dg3 = _new((n, 16, 16, C3), z2) if rot is None else rot.buf(rkey + ("dg3",), (n, 16, 16, C3))
             ws = _ws(z2)
@@ -1838,7 +1330,7 @@ class SVHNDecoderFn(Function):
                 else:
                     call("mvk_conv4s2_small_up_bwd_pre_y", ptr(out), ptr(drows), ptr(g3), RELU, ptr(w3), ptr(dg3), ptr(tw3), ptr(tb3),
                          ptr(tb2), ptr(ws), ws.numel(), n, 16, 16, C4, C3, ptr(a_dg3), stream_ptr())
-                tail_bwd_done(z2.device)
+                schedule.tail_bwd_done(z2.device)
             else:
                 call("mvk_conv4s2_small_up_bwd_pre", ptr(out), ptr(drows), ptr(g3), RELU, ptr(w3), ptr(dg3), ptr(tw3), ptr(tb3),
                      ptr(tb2), ptr(ws), ws.numel(), n, 16, 16, C4, C3, stream_ptr())
@@ -1871,15 +1363,15 @@ class SVHNDecoderFn(Function):
             am2 = (a_dg3, ctx.wamax[1] if a_dg3 is not None else None, a_dg2)
             am1 = (a_dg2, ctx.wamax[0], None)
             wam2, wam1 = (a_dg3, ctx.gamax[1]), (a_dg2, ctx.gamax[0])  # (max |U|, max |V|) of the two weight gradients
-        if ctx.f16 and wam1 is not None and LATE_LEAVES and z2.device in _DEFER_ACTIVE:
+        if ctx.f16 and wam1 is not None and schedule.LATE_LEAVES and schedule.scope(z2.device) is not None:
             # register-stationary weight gradients are this step's late leaves (what an MLP encoder's backward asks: heads_bwd_mlp;
             # a rotated step decides the same way, so that it launches exactly the kernels of the unrotated one)
-            big_late_leaves(z2.device)
-        rot = ctx.rot if (ctx.fused and ctx.rot is not None and rotation(z2.device) is ctx.rot) else None
+            schedule.big_late_leaves(z2.device)
+        rot = ctx.rot if (ctx.fused and ctx.rot is not None and schedule.rotation(z2.device) is ctx.rot) else None
         rot0 = rot if (rot is not None and ctx.rot_mode == 2) else None  # mode 2: only the first layer's weight gradient
         if rot0 is not None:
             rot = None
-        late = late_leaves(z2.device, dg3, g2, g1, z2)
+        late = schedule.late_leaves(z2.device, dg3, g2, g1, z2)
         if not late.on:
             rot = rot0 = None
             dw2 = conv_wgrad(dg3, g2, w2, n, 8, 8, C3, C2, amax=wam2)
@@ -1916,8 +1408,8 @@ class SVHNDecoderFn(Function):
         if late.on:  # the backward-data chain first, then the weight gradients beside whatever follows it
             if ctx.needs_input_grad[0]:
                 dz = _svhn_dz(dg1f, wp0, n, L, C1).view(ctx.z_shape)
-            dg2.record_stream(_side_stream(z2.device, 30))
-            dg1.record_stream(_side_stream(z2.device, 30))
+            dg2.record_stream(schedule._side_stream(z2.device, 30))
+            dg1.record_stream(schedule._side_stream(z2.device, 30))
             with late:
                 dw2 = conv_wgrad(dg3, g2, w2, n, 8, 8, C3, C2, amax=wam2)
                 dw1 = conv_wgrad(dg2, g1, w1, n, 4, 4, C2, C1, amax=wam1)
@@ -1940,7 +1432,7 @@ class SVHNDecoderFn(Function):
                     ws = _ws(z2)
                     call("mvk_unflatten_wgrad", ptr(z2), ptr(dg1f), ptr(tw0), n, L, C1, ptr(ws), ws.numel(), stream_ptr())
             if dw0 is not None or dw1 is not None or dw2 is not None:  # a gradient autograd itself accumulates: join now
-                torch.cuda.current_stream(z2.device).wait_stream(_side_stream(z2.device, 30))
+                torch.cuda.current_stream(z2.device).wait_stream(schedule._side_stream(z2.device, 30))
             return dz, dw0, db0, dw1, db1, dw2, db2, dw3, db3, None, None, None
         ws = _ws(z2)
         call("mvk_unflatten_wgrad", ptr(z2), ptr(dg1f), ptr(tw0), n, L, C1, ptr(ws), ws.numel(), stream_ptr())
@@ -2254,11 +1746,11 @@ class MoPoEPosteriorFn(Function):
         # path) — read from a kept buffer of that constant, and the assembly launch has no reader inside the step; else it comes
         # out of the assembly launch, which this node then waits for (or runs, when it was postponed)
         c = const_grad(dkld_rows) if dkld_rows is not None else None
-        gk = const_rows(dev, dkld_rows.numel(), c) if c is not None else None
+        gk = schedule.const_rows(dev, dkld_rows.numel(), c) if c is not None else None
         if gk is None:
-            wait_loss(dev)
+            schedule.wait_loss(dev)
             gk = _c(dkld_rows) if dkld_rows is not None else None
-        late_ready(dev)
+        schedule.late_ready(dev)
         saved = ctx.saved_tensors
         eps, subset_masks, sel = saved[:3]
         M = ctx.M
@@ -2298,8 +1790,8 @@ class MVTCAEPosteriorFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, djkl, dckl, *unused):
-        wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
-        late_ready(ctx.saved_tensors[0].device)
+        schedule.wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(ctx.saved_tensors[0].device)
         saved = ctx.saved_tensors
         eps = saved[0]
         M = ctx.M
@@ -2337,8 +1829,8 @@ class JMVAEPosteriorFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, dkld, dljm):
-        wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
-        late_ready(ctx.saved_tensors[0].device)
+        schedule.wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(ctx.saved_tensors[0].device)
         saved = ctx.saved_tensors
         eps, jmu, jlv = saved[:3]
         M = ctx.M
@@ -2358,9 +1850,6 @@ class JMVAEPosteriorFn(Function):
 # =====================================================================================================
 # Fused reconstruction NLL + scalar assembly (single autograd node producing the loss)
 # =====================================================================================================
-_UNIT_SEEDS = {}  # data_ptr -> tensor (kept alive): backward seeds known to hold exactly 1
-
-
 def unit_seed(like):
     """A ones tensor shaped like the loss `like`, registered as THE unit backward seed of its device: pass it as
     `loss.backward(gradient=...)` and ReconLossFn.backward needs no launch (autograd's own default seed is a fresh tensor
@@ -2379,32 +1868,16 @@ def is_unit_seed(g):
     return t is not None and t.shape == g.shape and t.device == g.device
 
 
-_TERMS_WS = {}  # (device, stream) -> the arrival counter + partials of mvk_reduce_terms_ws (zero between launches)
-
-
 def _reduce_terms(terms, n_terms, loss_sum_scale, out, loss):
     """The scalar assembly on the current stream, on several workgroups where a term is long (mvk_reduce_terms_ws)."""
-    key = (out.device, torch.cuda.current_stream(out.device).cuda_stream)
-    ws = _TERMS_WS.get(key)
+    ws = schedule.terms_workspace(out.device)
     if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            # ADVICE r5: a workspace made HERE would live in the capturing graph's private pool, zero-filled by a node of that
-            # graph only, and then be handed to every later capture through this cache.  The warm-up passes of GraphedStep run on
-            # another stream than the capture: inside a capture the launch takes the one-workgroup form, which needs no workspace
-            # (same sums in the same order per term; bit-identical results are tested for both forms)
-            call("mvk_reduce_terms", terms, n_terms, loss_sum_scale, ptr(out), ptr(loss), stream_ptr())
-            return
-        ws = torch.zeros(1 + 32 * 64, dtype=torch.float32, device=out.device)  # MVK_REDUCE_TERMS_WS_FLOATS
-        _TERMS_WS[key] = ws
+        # A capturing stream that has no workspace yet (schedule.terms_workspace makes none there).  The warm-up passes of
+        # GraphedStep run on another stream than the capture: inside a capture the launch takes the one-workgroup form, which
+        # needs no workspace (same sums in the same order per term; bit-identical results are tested for both forms)
+        call("mvk_reduce_terms", terms, n_terms, loss_sum_scale, ptr(out), ptr(loss), stream_ptr())
+        return
     call("mvk_reduce_terms_ws", terms, n_terms, loss_sum_scale, ptr(out), ptr(loss), ptr(ws), ws.numel(), stream_ptr())
-
-
-def terms_workspace(device, stream):
-    """Make the assembly's workspace of (device, stream) now, outside any capture (trainers/graph.py: before torch.cuda.graph, for
-    the capture stream and the late-leaf stream the assembly may run on).  Eager memory, zeroed once, left zero by every launch."""
-    key = (device, stream.cuda_stream)
-    if key not in _TERMS_WS:
-        _TERMS_WS[key] = torch.zeros(1 + 32 * 64, dtype=torch.float32, device=device)
 
 
 class ReconLossFn(Function):
@@ -2505,9 +1978,9 @@ class ReconLossFn(Function):
         # (spec["async_ok"]: they call wait_loss before reading a gradient this launch fills): the assembly is a leaf of the
         # step — nothing on the backward chain needs the loss VALUE — so it runs on the late-leaf stream, joined where the
         # deferred finishes run, instead of between the last forward and the first backward launch of the critical chain.
-        late = late_leaves(ref.device, *extras) if (ASYNC_LOSS and n_rec == 0 and spec.get("async_ok")) else None
+        late = schedule.late_leaves(ref.device, *extras) if (schedule.ASYNC_LOSS and n_rec == 0 and spec.get("async_ok")) else None
         dev = ref.device
-        if late is not None and late.on and ASSEMBLY_LAST and spec.get("assembly_last") and dev in _DEFER_ACTIVE:
+        if late is not None and late.on and schedule.ASSEMBLY_LAST and spec.get("assembly_last"):
             # The model vouches that NO backward node reads what this launch fills when the backward seed is the unit seed (its
             # posterior node takes the KL rows' constant gradient from const_grad): the launch is enqueued with the postponed
             # leaves at the end of the scope (run_last: the late-leaf stream, behind the large decoder's weight gradients) instead
@@ -2516,14 +1989,13 @@ class ReconLossFn(Function):
             keep = [out, loss] + [d for d in dextras if d is not None]
 
             def assemble():
-                _LOSS_POSTPONED.pop(dev, None)
                 _reduce_terms(terms, n_terms, spec["loss_sum_scale"], out, loss)
                 st = torch.cuda.current_stream(dev)
                 for t in keep:
                     t.record_stream(st)
 
-            if run_last(dev, assemble, *extras):
-                _LOSS_POSTPONED[dev] = assemble
+            if schedule.run_last(dev, assemble, *extras):
+                late.scope.loss = assemble  # wait_loss runs it for whoever reads what it fills before the scope ends
             else:
                 assemble()
         elif late is not None and late.on:
@@ -2533,7 +2005,7 @@ class ReconLossFn(Function):
             with late:
                 _reduce_terms(terms, n_terms, spec["loss_sum_scale"], out, loss)
                 st = torch.cuda.current_stream(ref.device)
-                _LOSS_EVENT[ref.device] = st.record_event()
+                late.scope.loss = st.record_event()
                 for t in [out, loss] + [d for d in dextras if d is not None]:
                     t.record_stream(st)
         else:
@@ -2567,7 +2039,7 @@ class ReconLossFn(Function):
                     register_const_grad(extras[j], cs[0])
             ctx.drecons = ctx.dextras = None
             return (None, None, *grads, *extras)
-        wait_loss(gloss.device)  # the seed launch below rewrites what the assembly launch filled
+        schedule.wait_loss(gloss.device)  # the seed launch below rewrites what the assembly launch filled
         gloss = _c(gloss.reshape(1))
         extras = [d if d is not None else _new(shape, gloss) for d, shape in zip(ctx.dextras, ctx.extra_shapes)]
         jobs = [(g.data_ptr(), g.numel(), 1.0, 0) for g in ctx.drecons if g is not None]
@@ -2598,8 +2070,8 @@ class GaussSampleKLFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dw, dkl):
-        wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
-        late_ready(ctx.saved_tensors[0].device)
+        schedule.wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(ctx.saved_tensors[0].device)
         eps, mu, lv = ctx.saved_tensors
         K, B, L = eps.shape
         dw = _c(dw) if dw is not None else None
@@ -2675,7 +2147,7 @@ class NexusTopNLLFn(Function):
         zs, rs, q, s2 = saved[:M], saved[M:2 * M], saved[2 * M], saved[2 * M + 1]
         if grows is None:
             return (None, None, None) + (None,) * M + tuple(torch.zeros_like(r) for r in rs)
-        wait_loss(grows.device)  # the rows' gradient may come out of the loss assembly launch
+        schedule.wait_loss(grows.device)  # the rows' gradient may come out of the loss assembly launch
         grows = _c(grows)
         dr = [torch.empty_like(r) for r in rs]
         marr = ptr_array(ctx.masks) if ctx.masks is not None else None

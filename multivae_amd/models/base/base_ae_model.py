@@ -11,7 +11,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ... import kernels
+from ... import kernels, schedule
 from ..nn.base_architectures import BaseDecoder, BaseEncoder
 from ..nn.default_architectures import BaseDictDecoders, BaseDictEncoders
 from .base_config import BaseMultiVAEConfig
@@ -60,7 +60,7 @@ class BaseMultiVAE(BaseModel):
 
     def _branch_order(self, inputs=None, names=None):
         """Modalities by decreasing input size: the first one keeps the caller's stream, the others get side streams
-        (kernels.run_branches), so the large modality's kernels are never queued behind the small ones."""
+        (schedule.run_branches), so the large modality's kernels are never queued behind the small ones."""
         names = list(self.encoders.keys()) if names is None else list(names)
         dims = self.input_dims or {}
 
@@ -252,10 +252,10 @@ class BaseMultiVAE(BaseModel):
         def decode_rows(zc, b0, b1):
             K, b = zc.shape[0], zc.shape[1]
             if private is None:
-                rec = kernels.run_branches(order, lambda m: self.decoders[m](zc).reconstruction, device)
+                rec = schedule.run_branches(order, lambda m: self.decoders[m](zc).reconstruction, device)
                 return kernels.recon_nll_rows([rec[m] for m in names], [x[b0:b1] for x in xs], dists, scales, K, b)
             ws = {m: private[m][0][:, b0:b1].contiguous() for m in names}
-            rec = kernels.run_branches(order, lambda m: self.decoders[m](torch.cat([zc, ws[m]], dim=-1)).reconstruction,
+            rec = schedule.run_branches(order, lambda m: self.decoders[m](torch.cat([zc, ws[m]], dim=-1)).reconstruction,
                                        device)
             rows = kernels.recon_nll_rows([rec[m] for m in names], [x[b0:b1] for x in xs], dists, scales, K, b)
             for m in names:  # -(ln p(w_m) - ln q(w_m | x_m)) as one more "row" of the log-weight

@@ -106,10 +106,10 @@ class _KLFn(Function):
             elif t.numel() == rows * L:
                 outs.append(d.view(t.shape))
             else:  # broadcast operand (indexed modulo its size): ordered column sums over the leading block
-                from ... import kernels
+                from ... import schedule
 
                 acc = torch.zeros(t.numel(), dtype=torch.float32, device=g.device)
-                ws = kernels._ws(g)
+                ws = schedule._ws(g)
                 call("mvk_colsum_acc", ptr(d), None, 0, ptr(acc), rows * L // t.numel(), t.numel(), ptr(ws), ws.numel(),
                      stream_ptr())
                 outs.append(acc.view(t.shape))

@@ -9,7 +9,7 @@ reconstruction kernel scores the two slabs as separate terms.
 """
 import torch
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
 from ..mvtcae.mvtcae_model import MVTCAE
@@ -45,7 +45,7 @@ class CRMVAE(BaseMultiVAE):
             nz = None if mod_noise is None else mod_noise[m].reshape(1, B, L)
             z_m[m], _ = kernels.GaussSampleKLFn.apply(self._noise((1, B, L), device, nz), mu, lv)
         dnames = [m for m in self.decoders.keys() if m in z_m]
-        rec = kernels.run_branches(self._branch_order(inputs, dnames),
+        rec = schedule.run_branches(self._branch_order(inputs, dnames),
                                    lambda m: self.decoders[m](torch.cat([z, z_m[m]], dim=0)).reconstruction, device)
         masks = inputs.masks if hasattr(inputs, "masks") else None
         pairs, pair_mod = [], []

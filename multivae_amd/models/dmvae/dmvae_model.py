@@ -12,7 +12,7 @@ from typing import Union
 import torch
 from torch import nn
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
 from ..nn.default_architectures import BaseDictDecodersMultiLatents, BaseDictEncoders_MultiLatents
@@ -57,7 +57,7 @@ class DMVAE(BaseMultiVAE):
     # -- posterior parameters ---------------------------------------------------------------------------------------
     def _encode_all(self, inputs, subset):
         order = self._branch_order(inputs, subset)
-        enc = kernels.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), inputs.data[order[0]].device)
+        enc = schedule.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), inputs.data[order[0]].device)
 
         def two_d(t):
             return t if t.dim() == 2 else t.unsqueeze(0)
@@ -118,7 +118,7 @@ class DMVAE(BaseMultiVAE):
             zs = torch.cat([z_joint[mods.index(m)]] + z_uni, dim=0)  # [E,B,L]
             return self.decoders[m](torch.cat([zs, w[m]], dim=-1)).reconstruction
 
-        rec = kernels.run_branches(self._branch_order(inputs, dnames), decode, device)
+        rec = schedule.run_branches(self._branch_order(inputs, dnames), decode, device)
         # one reconstruction term per (ELBO e, modality m); rows count when x_m is there and (e >= 1) x_e is there
         pairs, pair_mod, pair_e, pmasks = [], [], [], []
         for e in range(E):
@@ -241,7 +241,7 @@ class DMVAE(BaseMultiVAE):
                 b = b1 - b0
                 zc = z[:, b0:b1]
                 wc = {m: ws[m][:, b0:b1] for m in names}
-                rec = kernels.run_branches(order, lambda m: self.decoders[m](
+                rec = schedule.run_branches(order, lambda m: self.decoders[m](
                     torch.cat([zc, wc[m]], dim=-1).contiguous()).reconstruction, dev)
                 rows = kernels.recon_nll_rows([rec[m] for m in names], [x[b0:b1] for x in xs], dists, scales, K, b)
                 z_all = torch.cat([zc] + [wc[m] for m in names], dim=-1).contiguous()

@@ -4,7 +4,7 @@ from typing import Union
 
 import torch
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base.base_utils import ModelOutput
 from ..joint_models import BaseJointModel
 from ..nn.base_architectures import BaseJointEncoder
@@ -35,13 +35,13 @@ class JMVAE(BaseJointModel):
         mu, lv = joint.embedding, joint.log_covariance
         B, L = mu.shape
         device = mu.device
-        enc = kernels.run_branches(self._branch_order(inputs, names), lambda m: self.encoders[m](inputs.data[m]), device)
+        enc = schedule.run_branches(self._branch_order(inputs, names), lambda m: self.encoders[m](inputs.data[m]), device)
         mus = [enc[m].embedding for m in names]
         lvs = [enc[m].log_covariance for m in names]
         eps = self._noise((1, B, L), device, None if noise is None else noise.reshape(1, B, L))
         z, kld_rows, ljm_rows = kernels.JMVAEPosteriorFn.apply(eps, mu, lv, *mus, *lvs)
         dnames = list(self.decoders.keys())
-        rec = kernels.run_branches(self._branch_order(inputs, dnames), lambda m: self.decoders[m](z[0]).reconstruction,
+        rec = schedule.run_branches(self._branch_order(inputs, dnames), lambda m: self.decoders[m](z[0]).reconstruction,
                                    device)
         recons = [rec[m] for m in dnames]
         spec = self._recon_spec(dnames, inputs.data, None, 1, B)

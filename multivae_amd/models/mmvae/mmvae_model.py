@@ -11,7 +11,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from ... import _lib, kernels
+from ... import _lib, kernels, schedule
 from ...data.utils import drop_unused_modalities
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
@@ -58,7 +58,7 @@ class MMVAE(BaseMultiVAE):
             return mu, self.log_var_to_std(lv)
 
         order = self._branch_order(inputs, mods)
-        enc = kernels.run_branches(order, encode_one, inputs.data[order[0]].device)
+        enc = schedule.run_branches(order, encode_one, inputs.data[order[0]].device)
         mus = [enc[m][0] for m in mods]
         sds = [enc[m][1] for m in mods]
         B, L = mus[0].shape
@@ -85,7 +85,7 @@ class MMVAE(BaseMultiVAE):
             rec = self.decoders[r](zall).reconstruction
             return list(rec.reshape(M, K * B, *rec.shape[1:]).unbind(0))
 
-        dec = kernels.run_branches(self._branch_order(inputs, mods), decode_all, device)
+        dec = schedule.run_branches(self._branch_order(inputs, mods), decode_all, device)
         recons = [dec[r][c] for c in range(M) for r in mods]
         spec = self._recon_spec(mods, inputs.data, inputs.masks if masks is not None else None, K, B)
         loss = kernels.MMVAEObjectiveFn.apply(state, spec, M, dreg, *recons)
@@ -104,7 +104,7 @@ class MMVAE(BaseMultiVAE):
             return mu, kernels.std_from_logvar(lv, self._family)
 
         order = self._branch_order(inputs, mods)
-        return kernels.run_branches(order, encode_one, inputs.data[order[0]].device)
+        return schedule.run_branches(order, encode_one, inputs.data[order[0]].device)
 
     def encode(self, inputs, cond_mod: Union[list, str] = "all", N: int = 1, return_mean=False, **kwargs):
         """mmvae_model.py:312-363: the mean of the conditioning posteriors' means, or N samples from ONE conditioning

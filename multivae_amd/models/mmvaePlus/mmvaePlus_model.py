@@ -9,7 +9,7 @@ weighted by beta, and cross-modal decoder inputs take their private part from th
 import torch
 from torch import nn
 
-from ... import _lib, kernels
+from ... import _lib, kernels, schedule
 from ...data.utils import drop_unused_modalities
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
@@ -90,7 +90,7 @@ class MMVAEPlus(BaseMultiVAE):
             return mu, sd
 
         order = self._branch_order(inputs, mods)
-        enc = kernels.run_branches(order, encode_one, inputs.data[order[0]].device)
+        enc = schedule.run_branches(order, encode_one, inputs.data[order[0]].device)
         mus = [enc[m][0] for m in mods]
         sds = [enc[m][1] for m in mods]
         B = mus[0].shape[0]
@@ -132,7 +132,7 @@ class MMVAEPlus(BaseMultiVAE):
             rec = self.decoders[r](torch.cat(zins, dim=0)).reconstruction
             return list(rec.reshape(M, K * B, *rec.shape[1:]).unbind(0))
 
-        dec = kernels.run_branches(self._branch_order(inputs, mods), decode_all, device)
+        dec = schedule.run_branches(self._branch_order(inputs, mods), decode_all, device)
         recons = [dec[r][c] for c in range(M) for r in mods]
         spec = self._recon_spec(mods, inputs.data, inputs.masks if masks is not None else None, K, B)
         loss = kernels.MMVAEObjectiveFn.apply(state, spec, M, dreg, *recons)

@@ -12,7 +12,7 @@ from typing import Union
 
 import torch
 
-from ... import _lib, kernels
+from ... import _lib, kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
 from .mopoe_config import MoPoEConfig
@@ -126,13 +126,13 @@ class MoPoE(BaseMultiVAE):
                 side_work()  # BEHIND the short encoder: its stream also carries the step's weight-pack launch (kernels.pack_scope)
             return out
 
-        enc = kernels.run_branches(names, run, inputs.data[names[0]].device)
+        enc = schedule.run_branches(names, run, inputs.data[names[0]].device)
         return {m: enc[m] for m in self.encoders.keys()}
 
     def _posterior(self, inputs, K, noise=None, choice=None, want_stats=False):
         early = {}
         x0 = next(iter(inputs.data.values()))
-        if noise is None and x0.is_cuda and kernels.DEVICE_RNG and kernels.BRANCH_STREAMS and len(self.encoders) > 1 \
+        if noise is None and x0.is_cuda and kernels.DEVICE_RNG and schedule.BRANCH_STREAMS and len(self.encoders) > 1 \
                 and x0.dim() > 1:
             # the noise does not depend on the encoders: its launch rides at the head of the short encoder's branch stream
             # instead of sitting between the encoders and the posterior kernel on the main one
@@ -224,7 +224,7 @@ class MoPoE(BaseMultiVAE):
                     return ("rows", rows)
             return ("rec", dec(z_of(m)).reconstruction)
 
-        rec = kernels.run_branches(self._branch_order(inputs), decode, device, side_first=True)
+        rec = schedule.run_branches(self._branch_order(inputs), decode, device, side_first=True)
         plain = [m for m in names if rec[m][0] == "rec"]
         fused = [m for m in names if rec[m][0] == "rows"]
         recons = [rec[m][1] for m in plain]
@@ -237,9 +237,9 @@ class MoPoE(BaseMultiVAE):
                     loss_sum_scale=float(B),
                     # the backward nodes of every extra term (MoPoEPosteriorFn, GaussSampleKLFn, the fused tails) order themselves
                     # behind the assembly launch where they read what it fills: it may run beside the backward chain
-                    # — only when every fused term's node is one of the package's (kernels.orders_behind_loss): a user decoder's
+                    # — only when every fused term's node is one of the package's (schedule.orders_behind_loss): a user decoder's
                     # `reconstruction_nll` built from plain autograd ops would read the row gradients unordered
-                    async_ok=masks is None and all(kernels.orders_behind_loss(rec[m][1]) for m in fused),
+                    async_ok=masks is None and all(schedule.orders_behind_loss(rec[m][1]) for m in fused),
                     # ... and with the unit seed nothing reads what it fills: the posterior node takes the KL rows' constant
                     # gradient from the host (kernels.const_grad), the fused tails theirs — the launch may run LAST
                     assembly_last=masks is None and not style_kl)

@@ -13,7 +13,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
 from .mvae_config import MVAEConfig
@@ -53,7 +53,7 @@ class MVAE(BaseMultiVAE):
         names = list(self.encoders.keys())
         used = [m for m in names if any(m in s for s in subsets)]
         order = self._branch_order(inputs, used)
-        enc = kernels.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), inputs.data[order[0]].device)
+        enc = schedule.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), inputs.data[order[0]].device)
         ref = enc[used[0]].embedding
         if ref.dim() == 1:
             ref = ref.unsqueeze(0)
@@ -107,7 +107,7 @@ class MVAE(BaseMultiVAE):
         zs = dict(zip(names, outs[:len(names)]))  # every modality is in the joint subset
         kld_rows = outs[len(names)]
         dnames = [m for m in self.decoders.keys() if m in zs]
-        rec = kernels.run_branches(self._branch_order(inputs, dnames), lambda m: self.decoders[m](zs[m]).reconstruction,
+        rec = schedule.run_branches(self._branch_order(inputs, dnames), lambda m: self.decoders[m](zs[m]).reconstruction,
                                    device)
         # rows kept per subset (the reference filters the batch to samples with at least one modality of the subset,
         # :120-143) -- masks are inputs, one small host read per step in the incomplete-data case only

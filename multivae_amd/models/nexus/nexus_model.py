@@ -11,7 +11,7 @@ from typing import Union
 import torch
 from torch import nn
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_config import BaseAEConfig
 from ..base.base_utils import ModelOutput, rsample_from_gaussian
@@ -149,7 +149,7 @@ class Nexus(BaseMultiVAE):
 
         # first level: z_m ~ q(z_m | x_m), KL(q || N(0, I)) rows, reconstruction
         order = self._branch_order(inputs, names)
-        enc = kernels.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), device)
+        enc = schedule.run_branches(order, lambda m: self.encoders[m](inputs.data[m]), device)
         z, kl = {}, {}
         bottom_noise = noise.get("bottom") or {}
         for m in names:
@@ -158,10 +158,10 @@ class Nexus(BaseMultiVAE):
             eps = bottom_noise.get(m)
             z[m], kl[m] = kernels.GaussSampleKLFn.apply(self._noise((1, B, S), device, None if eps is None else eps.reshape(1, B, S)),
                                                         mu, lv)
-        rec = kernels.run_branches(order, lambda m: self.decoders[m](z[m][0]).reconstruction, device)
+        rec = schedule.run_branches(order, lambda m: self.decoders[m](z[m][0]).reconstruction, device)
         # second level: messages of the detached z_m, their mean over the kept modalities, z_sigma
         zd = {m: z[m][0].detach() for m in names}
-        msg = kernels.run_branches(order, lambda m: self.top_encoders[m](zd[m]).embedding, device)
+        msg = schedule.run_branches(order, lambda m: self.top_encoders[m](zd[m]).embedding, device)
         msgs = [msg[m] for m in names]
         if bmasks is not None:
             agg, keep_used = kernels.NexusAggregateFn.apply(bmasks, None, None, 0.0, *msgs)
@@ -180,7 +180,7 @@ class Nexus(BaseMultiVAE):
         zj, jkl = kernels.GaussSampleKLFn.apply(self._noise((1, B, L), device, None if jeps is None else jeps.reshape(1, B, L)),
                                                 jout.embedding, jout.log_covariance)
         tnames = list(self.top_decoders.keys())
-        top = kernels.run_branches(order, lambda m: self.top_decoders[m](zj[0]).reconstruction, device)
+        top = schedule.run_branches(order, lambda m: self.top_decoders[m](zj[0]).reconstruction, device)
         rs = [top[m].reshape(B, -1) for m in tnames]
         tmasks = None if bmasks is None else [bmasks[names.index(m)] for m in tnames]
         top_rows, _ = kernels.NexusTopNLLFn.apply(tmasks, [float(self.gammas[m]) for m in tnames],

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ... import kernels
+from ... import kernels, schedule
 from ..base.base_config import BaseAEConfig
 from ..base.base_utils import ModelOutput
 from .base_architectures import BaseDecoder, BaseEncoder, BaseJointEncoder, BaseMultilatentEncoder
@@ -63,7 +63,7 @@ class Decoder_AE_MLP(BaseDecoder):
         return ModelOutput(reconstruction=out)
 
     def late_leaf_params(self):
-        """The parameters whose gradients are leaves of the backward pass that a rotated step (kernels.Rotation) produces at the
+        """The parameters whose gradients are leaves of the backward pass that a rotated step (schedule.Rotation) produces at the
         head of the NEXT step: trainers.FlatParams keeps them together at the end of its buffers."""
         l0, l1 = self.layers[0][0], self.layers[1][0]
         return [l0.weight, l1.weight, l1.bias] if self.depth == 2 else []
@@ -164,7 +164,7 @@ class MultipleHeadJointEncoder(BaseJointEncoder):
         assert list(x.keys()) == list(self.encoders.keys())
         names = list(self.encoders.keys())
         dev = x[names[0]].device
-        outs = kernels.run_branches(names, lambda m: self.encoders[m](x[m])["embedding"], dev)
+        outs = schedule.run_branches(names, lambda m: self.encoders[m](x[m])["embedding"], dev)
         h = torch.cat([outs[m] for m in names], dim=1)
         params = []
         for seq in self.enc:

@@ -64,7 +64,7 @@ class Decoder_VAE_SVHN(BaseDecoder):
         return [(d[0].weight, "unflatten"), (d[2].weight, True, True), (d[4].weight, True, True), (d[6].weight, True, False)]
 
     def late_leaf_params(self):
-        """The weights whose gradients are leaves of the backward pass that a rotated step (kernels.Rotation) produces at the
+        """The weights whose gradients are leaves of the backward pass that a rotated step (schedule.Rotation) produces at the
         head of the NEXT step: trainers.FlatParams keeps them together at the end of its buffers."""
         d = self.dec
         return [d[0].weight, d[2].weight, d[4].weight]

@@ -21,7 +21,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from ... import kernels
+from ... import kernels, schedule
 from ...data.datasets.base import DatasetOutput
 from ...models.base.base_model import BaseModel
 from ..flat import FlatParams, FusedAdam
@@ -329,7 +329,7 @@ class BaseTrainer:
             # always through the flat buffer: torch's own zero_grad() sets .grad to None, backward() would then
             # allocate gradients OUTSIDE the buffer the all-reduce below exchanges
             self.flat.zero_grad()
-            with kernels.deferred_reductions(self.flat):  # one launch finishes every weight / bias gradient
+            with schedule.deferred_reductions(self.flat):  # one launch finishes every weight / bias gradient
                 # the registered unit seed (cuda): the loss node's backward then needs no launch (kernels.unit_seed)
                 loss.backward(gradient=kernels.unit_seed(loss) if loss.is_cuda else None)
             if not isinstance(self.optimizer, FusedAdam):

@@ -52,7 +52,7 @@ class BaseTrainerConfig(BaseConfig):
     # the event node alone): off by default, worth trying where the optimizer launch or the collective is a large part of the step
     graph_optimizer: bool = False
     overlap_collective: bool = False
-    # with use_hip_graph, single GPU, FusedAdam(zero_grad_in_step): the ROTATED step (trainers/graph.py, kernels.Rotation) — the
+    # with use_hip_graph, single GPU, FusedAdam(zero_grad_in_step): the ROTATED step (trainers/graph.py, schedule.Rotation) — the
     # decoders' late weight gradients of step N, their finishes and their share of optimizer.step() run at the head of replay
     # N + 1 beside the encoders' forward pass; the trainer drains what is pending before anything but another replay reads the
     # parameters (eager steps of ragged batches, the end of an epoch: evaluation, checkpoints, callbacks).  Exact (parameters

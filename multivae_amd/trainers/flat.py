@@ -19,7 +19,7 @@ class FlatParams:
         if not self.params:
             raise ValueError("model has no trainable parameters")
         # Parameters a module announces as `late_leaf_params()` (the decoders' weights whose gradients a rotated step produces
-        # at the head of the NEXT step: kernels.Rotation) sit together at the END of the buffers, so that the step's two
+        # at the head of the NEXT step: schedule.Rotation) sit together at the END of the buffers, so that the step's two
         # optimizer launches (everything else / the rotated range) and the two halves of a data-parallel collective are one
         # contiguous range each.  The layout inside the buffer is private: state dicts and `dense()` go by parameter.
         late_first, late_rest = [], []  # per announcing module: its FIRST entry (by convention the first layer's weight, the

@@ -12,13 +12,13 @@ the step is copy batch -> ONE replay.
 
 Data parallel (`overlap=True`, one process per GPU): the collective stays outside the graph (RCCL launches are not captured), but
 it no longer waits for the whole backward pass: the graph carries an external event-record node where everything but the last
-encoder's gradients is final (kernels.OverlapPoint), `reduce_and_step` starts that part's all-reduce on a communication stream
+encoder's gradients is final (schedule.OverlapPoint), `reduce_and_step` starts that part's all-reduce on a communication stream
 behind the event — beside the rest of the backward pass —, the remainder behind the replay, then Adam:
 copy batch -> replay || all-reduce(early ranges) -> all-reduce(late ranges) -> adam.  The reference's DDP overlaps its bucket
 reductions with loss.backward() the same way (trainers/base/base_trainer.py:116-117,359).
 
 Rotated (`rotate=optimizer`, single GPU): the decoders' weight-gradient leaves of step N, their finishes and their share of the
-optimizer run at the HEAD of replay N + 1 on a branch of their own, beside the encoders' forward pass (kernels.Rotation); the
+optimizer run at the HEAD of replay N + 1 on a branch of their own, beside the encoders' forward pass (schedule.Rotation); the
 caller's optimizer.step() behind replay N covers everything else and leaves its scalars on the device for that branch.
 `drain()` applies what is pending (end of an epoch, before evaluation / a checkpoint / an eager step); parameters after N
 replays + drain are bit for bit those of N unrotated steps.
@@ -30,7 +30,7 @@ import os
 
 import torch
 
-from .. import _lib, kernels
+from .. import _lib, kernels, schedule
 from ..data.datasets.base import DatasetOutput
 
 
@@ -48,12 +48,12 @@ class GraphedStep:
         if rotate is not None and (optimizer is not None or overlap or not hasattr(rotate, "set_rotation")):
             raise ValueError("GraphedStep(rotate=...) excludes optimizer= / overlap= and needs a trainers.FusedAdam")
         self.rot_opt = rotate
-        self.rotation = kernels.Rotation(dev) if rotate is not None else None
+        self.rotation = schedule.Rotation(dev) if rotate is not None else None
         self.rotated = False
         self.optimizer = optimizer if (optimizer is not None and getattr(optimizer, "zero_grad_in_step", False)
                                        and hasattr(optimizer, "step_captured") and not overlap) else None
         self.includes_optimizer = self.optimizer is not None
-        self.overlap_point = kernels.OverlapPoint(dev) if overlap else None
+        self.overlap_point = schedule.OverlapPoint(dev) if overlap else None
         self.early_ranges = self.late_ranges = None
         if self.optimizer is not None:
             self.optimizer.sync_device_state()  # allocates the device scalars the captured launches point at
@@ -70,7 +70,7 @@ class GraphedStep:
         prof = kernels.PROFILE.pop("recon_nll", None)  # host-timed events cannot be recorded into a graph
         try:
             cur = torch.cuda.current_stream(dev)
-            side = kernels._side_stream(dev, 62)  # a dedicated stream (not one of torch's pooled ones: _lib.new_stream)
+            side = schedule._side_stream(dev, 62)  # a dedicated stream (not one of torch's pooled ones: _lib.new_stream)
             side.wait_stream(cur)
             with torch.cuda.stream(side):  # eager warm-up: fills every cache (scratch, packed masks, autotuned paths)
                 for _ in range(max(int(warmup), 2 if self.rotation is not None else 1)):
@@ -87,8 +87,8 @@ class GraphedStep:
                     self.rotated = True
                 else:  # nothing in this model registers rotatable leaves: an ordinary captured step
                     self.rotation = None
-            for st in (cur, kernels._side_stream(dev, 30)):  # the loss assembly's workspace: eager memory, made outside the capture
-                kernels.terms_workspace(dev, st)
+            for st in (cur, schedule._side_stream(dev, 30)):  # the loss assembly's workspace: eager memory, made outside the capture
+                schedule.terms_workspace(dev, st)
             self.graph = torch.cuda.CUDAGraph()
             # (stream priorities were tried: capturing the main branch, or the side branches, on a priority -1 stream
             # makes the replayed step 3.0-3.1 ms instead of 1.9)
@@ -117,27 +117,22 @@ class GraphedStep:
         kw = dict(self.fwd_kwargs)
         if self.noise is not None:
             kw["noise"] = self.noise
-        dev = self.flat.flat.device
         opt = self.optimizer if capture else None  # the eager warm-up passes must not move the parameters
-        if opt is not None:
-            kernels.set_prelude(dev, opt.prepare_captured)  # depends on nothing of the step: head of the first side branch
-        if self.overlap_point is not None:
-            self.overlap_point.begin()
         rot = self.rotation
+        # the optimizer's scalar preparation depends on nothing of the step: the scope's prelude (head of the first side branch)
+        step = schedule.deferred_reductions(self.flat, prelude=opt.prepare_captured if opt is not None else None,
+                                            overlap=self.overlap_point, rotation=rot)
         try:
-            with kernels.deferred_reductions(self.flat):
+            with step:
                 if rot is not None:  # the head branch: the previous step's leaves, finishes, update, packs
                     rot.begin_step(self.rot_opt.rot_update if (capture and self.rotated) else None)
                 out = self.model(self.inputs, **kw)
                 # the registered unit seed: filled once (not one launch per replay), and ReconLossFn.backward launches nothing
                 out.loss.backward(gradient=kernels.unit_seed(out.loss))
             if opt is not None:
-                kernels.run_prelude(dev)  # no branch took it: here, in front of the update
+                step.run_prelude()  # no branch took it: here, in front of the update
                 opt.step_captured()
         finally:
-            kernels._PRELUDE.pop(dev, None)
-            if self.overlap_point is not None:
-                self.overlap_point.end()
             if rot is not None:
                 rot.end_step()
         return out
@@ -198,7 +193,7 @@ class GraphedStep:
         anything but another replay reads the parameters or the optimizer state (evaluation, checkpoint, eager step)."""
         if not self.rotated or not self.rot_opt._rot_dirty:
             return
-        with kernels.deferred_reductions(self.flat):
+        with schedule.deferred_reductions(self.flat):
             self.rotation.run_pending()
         self.rot_opt.rot_update()
         self.rot_opt.rot_drained()
@@ -211,7 +206,7 @@ class GraphedStep:
         flat, dev = self.flat, self.flat.flat.device
         cur = torch.cuda.current_stream(dev)
         if self.early_ranges and self.late_ranges and os.environ.get("MVK_OVERLAP") != "2":  # 2: event node captured, serial collective (A/B)
-            comm = kernels._side_stream(dev, 61)
+            comm = schedule._side_stream(dev, 61)
             kernels.call("mvk_stream_wait_event", kernels.C.c_void_p(comm.cuda_stream), self.overlap_point.event)
             with torch.cuda.stream(comm):
                 flat.all_reduce_mean_ranges(self.early_ranges)  # starts where the graph's event node fires

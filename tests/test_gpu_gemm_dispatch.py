@@ -168,7 +168,7 @@ class Prep:
     outs: list
     agg: object = None           # () -> torch fp32 result on the GPU of output 0 (aggregate check (b))
     det: bool = True             # ordered reductions: bit-identical repeat
-    deferred: bool = False       # outputs are views of a flat gradient buffer inside kernels.deferred_reductions
+    deferred: bool = False       # outputs are views of a flat gradient buffer inside schedule.deferred_reductions
     flags: int = 0               # mvk_debug_set_flags for the call
     keep: list = field(default_factory=list)
 
@@ -888,7 +888,7 @@ def _flags(f):
 def execute(p):
     """One launch from the case's initial buffers; returns the buffers (device) and the run closure's kernels are profiled
     by the caller."""
-    from multivae_amd import kernels as KK
+    from multivae_amd import schedule
 
     d = dev()
     shapes = [o.shape or tuple(o.ref.shape) for o in p.outs]
@@ -913,7 +913,7 @@ def execute(p):
         _flags(p.flags)
         try:
             if flat is not None:
-                with KK.deferred_reductions(flat):
+                with schedule.deferred_reductions(flat):
                     p.call(bufs)
             else:
                 p.call(bufs)

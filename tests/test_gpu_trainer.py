@@ -109,12 +109,12 @@ def _mnist_svhn_mopoe(d, K=3, L=8, seed=0):
 def _run_steps(d, steps, graphed, branch_streams=True, B=64, K=3, L=8):
     """Losses and final parameters of `steps` Adam steps; the two modality branches on separate streams or not,
     launches enqueued from Python or replayed from one hipGraph."""
-    from multivae_amd import kernels
+    from multivae_amd import schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.trainers import FlatParams, FusedAdam, GraphedStep
 
-    old = kernels.BRANCH_STREAMS
-    kernels.BRANCH_STREAMS = branch_streams
+    old = schedule.BRANCH_STREAMS
+    schedule.BRANCH_STREAMS = branch_streams
     try:
         model = _mnist_svhn_mopoe(d, K=K, L=L)
         flat = FlatParams(model)
@@ -137,7 +137,7 @@ def _run_steps(d, steps, graphed, branch_streams=True, B=64, K=3, L=8):
         torch.cuda.synchronize()
         return losses, flat.dense(flat.flat.detach()).cpu().clone()
     finally:
-        kernels.BRANCH_STREAMS = old
+        schedule.BRANCH_STREAMS = old
 
 
 def _same_training(r1, r2, lr=1e-3):
@@ -151,7 +151,7 @@ def _same_training(r1, r2, lr=1e-3):
 
 
 def test_branch_streams_do_not_change_the_result():
-    """Encoders / decoders of the two modalities on separate HIP streams (kernels.run_branches) vs one stream."""
+    """Encoders / decoders of the two modalities on separate HIP streams (schedule.run_branches) vs one stream."""
     d = torch.device("cuda:0")
     _same_training(_run_steps(d, 4, graphed=False, branch_streams=False), _run_steps(d, 4, graphed=False, branch_streams=True))
 
@@ -165,12 +165,12 @@ def test_graph_replay_matches_eager():
 def test_user_decoder_with_autograd_reconstruction_nll_is_ordered_behind_the_loss_assembly():
     """the fused-tail protocol is duck-typed — a USER decoder may implement `reconstruction_nll` with ordinary
     autograd ops.  Its backward reads the row gradients the loss-assembly launch fills, so that launch must not move to the
-    late-leaf stream for it (in a captured graph: a missing dependency, silently wrong gradients).  `kernels.orders_behind_loss`
+    late-leaf stream for it (in a captured graph: a missing dependency, silently wrong gradients).  `schedule.orders_behind_loss`
     keeps `async_ok` off unless every fused term comes from one of the package's nodes: the gradients of such a model — eager and
     replayed — equal the generic path's (forward + likelihood kernel)."""
     import math
 
-    from multivae_amd import kernels
+    from multivae_amd import kernels, schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.models.base.base_config import BaseAEConfig
     from multivae_amd.models.nn.default_architectures import Decoder_AE_MLP
@@ -189,8 +189,8 @@ def test_user_decoder_with_autograd_reconstruction_nll_is_ordered_behind_the_los
     inputs = DatasetOutput(data=dict(mnist=torch.rand(B, 1, 28, 28, generator=g).to(d), svhn=torch.rand(B, 3, 32, 32, generator=g).to(d)))
     eps = torch.randn(K, B, L, generator=g).to(d)
     seen = []
-    orig = kernels.orders_behind_loss
-    kernels.orders_behind_loss = lambda rows: (seen.append(orig(rows)), seen[-1])[1]
+    orig = schedule.orders_behind_loss
+    schedule.orders_behind_loss = lambda rows: (seen.append(orig(rows)), seen[-1])[1]
     try:
         res = {}
         for mode in ("generic", "user eager", "user graph"):
@@ -207,17 +207,17 @@ def test_user_decoder_with_autograd_reconstruction_nll_is_ordered_behind_the_los
                 out = gs(inputs, eps)
             else:
                 flat.zero_grad()
-                with kernels.deferred_reductions(flat):
+                with schedule.deferred_reductions(flat):
                     out = model(inputs, noise=eps)
                     out.loss.backward(gradient=kernels.unit_seed(out.loss))
             torch.cuda.synchronize()
             res[mode] = (float(out.loss), flat.dense(flat.grad).cpu().clone())
     finally:
-        kernels.orders_behind_loss = orig
+        schedule.orders_behind_loss = orig
     assert seen and not any(seen)  # the user decoder's rows were recognised as foreign (it is asked first: all() stops there)
     stock = _mnist_svhn_mopoe(d, K=K, L=L)  # ... and the package's own fused tails as its own
     rows = stock.decoders["svhn"].reconstruction_nll(torch.randn(K, B, L, device=d, requires_grad=True), inputs.data["svhn"], "normal", 1.0)
-    assert rows is not None and kernels.orders_behind_loss(rows)
+    assert rows is not None and schedule.orders_behind_loss(rows)
     ref_l, ref_g = res["generic"]
     for mode in ("user eager", "user graph"):
         l, gr = res[mode]
@@ -280,10 +280,10 @@ def test_optimizer_inside_the_graph_matches_the_host_scalar_step(amsgrad):
 def test_loss_assembly_postponed_to_the_end_of_the_step(seed_kind):
     """Round 6: with the unit backward seed nothing inside the step reads what the loss assembly fills (the fused tails hold their
     gradient pre-multiplied, the posterior node takes the KL rows' constant from the host), so MoPoE lets the launch run LAST
-    (`spec["assembly_last"]`, kernels.ASSEMBLY_LAST) — loss, every metric and the whole gradient buffer are bit for bit those of
+    (`spec["assembly_last"]`, schedule.ASSEMBLY_LAST) — loss, every metric and the whole gradient buffer are bit for bit those of
     the launch at the head of the backward pass; with autograd's own seed (a tensor whose value the host does not know) the
-    first reader runs the postponed launch itself (kernels.wait_loss) — same result."""
-    from multivae_amd import kernels
+    first reader runs the postponed launch itself (schedule.wait_loss) — same result."""
+    from multivae_amd import kernels, schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.trainers import FlatParams
 
@@ -292,17 +292,17 @@ def test_loss_assembly_postponed_to_the_end_of_the_step(seed_kind):
     g = torch.Generator().manual_seed(21)
     inputs = DatasetOutput(data=dict(mnist=torch.rand(B, 1, 28, 28, generator=g).to(d), svhn=torch.rand(B, 3, 32, 32, generator=g).to(d)))
     eps = torch.randn(K, B, L, generator=g).to(d)
-    old = kernels.ASSEMBLY_LAST
+    old = schedule.ASSEMBLY_LAST
     res, postponed = [], []
-    orig_run_last = kernels.run_last
+    orig_run_last = schedule.run_last
     try:
         for last in (False, True):
-            kernels.ASSEMBLY_LAST = last
-            kernels.run_last = lambda dev, fn, *a, **k: (postponed.append((last, getattr(fn, "__name__", ""))), orig_run_last(dev, fn, *a, **k))[1]
+            schedule.ASSEMBLY_LAST = last
+            schedule.run_last = lambda dev, fn, *a, **k: (postponed.append((last, getattr(fn, "__name__", ""))), orig_run_last(dev, fn, *a, **k))[1]
             model = _mnist_svhn_mopoe(d, K=K, L=L)
             flat = FlatParams(model)
             flat.zero_grad()
-            with kernels.deferred_reductions(flat):
+            with schedule.deferred_reductions(flat):
                 out = model(inputs, noise=eps)
                 if seed_kind == "unit seed":
                     out.loss.backward(gradient=kernels.unit_seed(out.loss))
@@ -311,7 +311,7 @@ def test_loss_assembly_postponed_to_the_end_of_the_step(seed_kind):
             torch.cuda.synchronize()
             res.append((float(out.loss.detach()), float(out.loss_sum.detach()), {k: float(v.detach()) for k, v in out.metrics.items()}, flat.grad.detach().clone()))
     finally:
-        kernels.ASSEMBLY_LAST, kernels.run_last = old, orig_run_last
+        schedule.ASSEMBLY_LAST, schedule.run_last = old, orig_run_last
     assert (True, "assemble") in postponed and (False, "assemble") not in postponed  # the launch WAS handed to the postponed leaves
     (l0, s0, m0, g0), (l1, s1, m1, g1) = res
     assert l0 == l1 and s0 == s1 and m0 == m1
@@ -321,14 +321,14 @@ def test_loss_assembly_postponed_to_the_end_of_the_step(seed_kind):
 @pytest.mark.parametrize("amsgrad,which", [(False, "both"), (True, "both"), (False, "svhn"), (False, "mlp"), (False, "small"), (True, "small")])
 def test_rotated_step_is_bit_identical(amsgrad, which):
     """GraphedStep(rotate=optimizer) — the decoders' late weight gradients of step N, their ordered finishes,
-    their share of Adam and the weight packs that read them run at the HEAD of replay N + 1 (kernels.Rotation), the caller's
+    their share of Adam and the weight packs that read them run at the HEAD of replay N + 1 (schedule.Rotation), the caller's
     optimizer.step() covers the rest and publishes its scalars (mvk_adam_step_pub / mvk_adam_step_dev).  Same noise, same
     kernels, same scalars: after 7 steps + drain the parameters, both Adam moments (and max_exp_avg_sq) and every loss are
     BIT FOR BIT those of the unrotated GraphedStep — with a learning-rate change mid-run, a drain + eager step in the middle
     (the ragged last batch of an epoch), warm-up and capture moving nothing, and the optimizer refusing an eager step or a
     state_dict while an update is pending.  Decoder rows = 128 x 10: the scaled-fp16 convolution chain and the MLP decoder's
     fused tail (the two nodes that register rotatable leaves) take the batch."""
-    from multivae_amd import kernels
+    from multivae_amd import schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.trainers import FlatParams, FusedAdam, GraphedStep
 
@@ -337,9 +337,9 @@ def test_rotated_step_is_bit_identical(amsgrad, which):
     g = torch.Generator().manual_seed(11)
     inputs = DatasetOutput(data=dict(mnist=torch.rand(B, 1, 28, 28, generator=g).to(d), svhn=torch.rand(B, 3, 32, 32, generator=g).to(d)))
     noise = [torch.randn(K, B, L, generator=g).to(d) for _ in range(7)]
-    old = kernels.ROT_SVHN, kernels.ROT_MLP
+    old = schedule.ROT_SVHN, schedule.ROT_MLP
     # which leaves are rotated: every weight-gradient leaf of both decoders / of one of them / only the two first-layer ones ("small")
-    kernels.ROT_SVHN, kernels.ROT_MLP = {"both": (1, 1), "svhn": (1, 0), "mlp": (0, 1), "small": (2, 2)}[which]
+    schedule.ROT_SVHN, schedule.ROT_MLP = {"both": (1, 1), "svhn": (1, 0), "mlp": (0, 1), "small": (2, 2)}[which]
     res = []
     try:
         for rotate in (False, True):
@@ -367,7 +367,7 @@ def test_rotated_step_is_bit_identical(amsgrad, which):
                             opt.step()
                     gs.drain()
                     opt.zero_grad()
-                    with kernels.deferred_reductions(flat):
+                    with schedule.deferred_reductions(flat):
                         out = model(inputs, noise=eps)
                         out.loss.backward()
                     opt.step()
@@ -384,7 +384,7 @@ def test_rotated_step_is_bit_identical(amsgrad, which):
             res.append((losses, flat.dense(flat.flat).cpu().clone(), flat.dense(opt.m).cpu().clone(), flat.dense(opt.v).cpu().clone(),
                         flat.dense(opt.vmax).cpu().clone() if amsgrad else None))
     finally:
-        kernels.ROT_SVHN, kernels.ROT_MLP = old
+        schedule.ROT_SVHN, schedule.ROT_MLP = old
     (l0, p0, m0, v0, x0), (l1, p1, m1, v1, x1) = res
     assert l0 == l1, (l0, l1)
     assert torch.equal(p0, p1), float((p0 - p1).abs().max())
@@ -435,11 +435,11 @@ def test_fused_decoder_tail_matches_the_generic_path(K, B):
 
 
 def test_deferred_reductions_match_immediate_finishes():
-    """kernels.deferred_reductions (mvk_defer_begin / _end): every ordered finish of a weight / bias gradient queued and
+    """schedule.deferred_reductions (mvk_defer_begin / _end): every ordered finish of a weight / bias gradient queued and
     run in one launch at the end of the backward pass vs one launch each behind its producer.  Same partial results, a
     different (fixed) summation tree for the column-sum finishes; bit-identical from run to run; nothing left pending.
     n = K * B = 2560 images: the register-stationary convolution kernels and their slabs are on the path."""
-    from multivae_amd import _lib, kernels
+    from multivae_amd import _lib, schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.trainers import FlatParams
 
@@ -455,7 +455,7 @@ def test_deferred_reductions_match_immediate_finishes():
     def run(deferred, settled=True):
         flat.zero_grad()
         if deferred:
-            with kernels.deferred_reductions(flat) as ctx:
+            with schedule.deferred_reductions(flat) as ctx:
                 assert ctx.on
                 out = model(inputs, noise=eps)
                 out.loss.backward()
@@ -468,7 +468,7 @@ def test_deferred_reductions_match_immediate_finishes():
         return float(out.loss.detach()), flat.grad.detach().clone()
 
     l0, g0 = run(False)
-    run(True, settled=False)  # the arena grows to what the step asks for (kernels.deferred_reductions): which finishes are queued settles here
+    run(True, settled=False)  # the arena grows to what the step asks for (schedule.deferred_reductions): which finishes are queued settles here
     l1, g1 = run(True)
     l2, g2 = run(True)
     assert l0 == l1 == l2
@@ -483,7 +483,7 @@ def test_deferred_reductions_match_immediate_finishes():
 def test_deferred_reductions_fall_back_when_the_arena_is_full():
     """A 1 MB arena holds a few of the ~30 partial-result regions of a step: the producers that do not fit finish
     immediately (their own launch), the others are queued — same gradients as with the full arena."""
-    from multivae_amd import kernels
+    from multivae_amd import schedule
     from multivae_amd.data.datasets.base import DatasetOutput
     from multivae_amd.trainers import FlatParams
 
@@ -498,19 +498,18 @@ def test_deferred_reductions_fall_back_when_the_arena_is_full():
 
     def run():
         flat.zero_grad()
-        with kernels.deferred_reductions(flat):
+        with schedule.deferred_reductions(flat):
             out = model(inputs, noise=eps)
             out.loss.backward()
         torch.cuda.synchronize()
         return flat.grad.detach().clone()
 
     full = run()
-    saved = kernels._ARENA.get(d)
-    kernels._ARENA[d] = torch.empty(1 << 18, dtype=torch.float32, device=d)
+    saved = schedule.swap_arena(d, torch.empty(1 << 18, dtype=torch.float32, device=d))
     try:
         small = run()
     finally:
-        kernels._ARENA[d] = saved
+        schedule.swap_arena(d, saved)
     scale = float(full.abs().max())
     assert float((small - full).abs().max()) <= 2e-6 * scale
 

@@ -2,12 +2,12 @@ import sys, os, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import test_gpu_trainer as T
-from multivae_amd import kernels
+from multivae_amd import schedule
 from multivae_amd.data.datasets.base import DatasetOutput
 from multivae_amd.trainers import FlatParams
 d = torch.device("cuda:0")
 def grads(streams, B=64, K=3, L=8):
-    kernels.BRANCH_STREAMS = streams
+    schedule.BRANCH_STREAMS = streams
     model = T._mnist_svhn_mopoe(d, K=K, L=L)
     flat = FlatParams(model)
     g = torch.Generator().manual_seed(3)

@@ -5,7 +5,7 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from multivae_amd import _lib, kernels as K  # noqa: E402
+from multivae_amd import _lib, kernels as K, schedule  # noqa: E402
 from multivae_amd._lib import call, ptr, stream_ptr  # noqa: E402
 
 lib = _lib.load()
@@ -19,7 +19,7 @@ U = torch.rand(n, Cu, 2 * h, 2 * h, generator=g).to(d)
 dU = torch.randn(n, Cu, 2 * h, 2 * h, generator=g).to(d)
 dV = torch.empty_like(V)
 dW, db, dbv = torch.zeros_like(W), torch.zeros(Cu, device=d), torch.zeros(Cv, device=d)
-ws = K._ws(V)
+ws = schedule._ws(V)
 buf = torch.zeros(512 * 4 * 8, dtype=torch.int64, device=d)
 lib.mvk_smallup_debug_buffer(ctypes.c_void_p(buf.data_ptr()))
 for _ in range(2):

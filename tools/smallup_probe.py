@@ -6,7 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from multivae_amd import _lib, kernels as K  # noqa: E402
+from multivae_amd import _lib, kernels as K, schedule  # noqa: E402
 from multivae_amd._lib import call, ptr, stream_ptr  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 5120
@@ -21,7 +21,7 @@ U = torch.empty(n, Cu, 2 * h, 2 * h, device=d)
 dU = torch.randn(n, Cu, 2 * h, 2 * h, generator=g).to(d)
 dV = torch.empty_like(V)
 dW, db, dbv = torch.zeros_like(W), torch.zeros_like(b), torch.zeros(Cv, device=d)
-ws = K._ws(V)
+ws = schedule._ws(V)
 
 
 def fwd():
