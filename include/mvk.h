@@ -875,8 +875,10 @@ int mvk_prof_count(void);     /* records taken since mvk_prof_enable */
 int mvk_prof_calibrate(void* device_ticks, int n, void* stream);
 int mvk_prof_clock_khz(void); /* rate of the stamped clock */
 
-/* Measurement hooks for experiment builds of the library (-DMVK_PHASES: per-phase cycle counters of the GEMM main
- * loop accumulated into an 8-entry device buffer; -DMVK_EXPER: ablation switches).  Inert in the shipped build. */
+/* Measurement hooks.  The phase buffer is read by a -DMVK_PHASES build of the library only (per-phase cycle counters of
+ * the GEMM main loop accumulated into an 8-entry device buffer) and is inert in the shipped build.  The flags are host-side
+ * dispatch bits in every build: 0x100 / 0x200 take the register-stationary 4x4 stride-2 kernels never / for every batch
+ * size, 0x400 / 0x800 the same for the register-stationary 3x3 kernels. */
 void mvk_debug_set_phase_buffer(unsigned long long* device_counters);
 void mvk_debug_set_flags(int flags);
 

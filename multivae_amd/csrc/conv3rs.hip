@@ -28,39 +28,11 @@
 
 #include "bf3.hpp"
 
-#ifdef MVK_NO_RFL
-#define MVK_RFL(x) (x)
-#else
-#define MVK_RFL(x) __builtin_amdgcn_readfirstlane(x)
-#endif
-
-#ifndef MVK_C3_SCHED
-#define MVK_C3_SCHED 4  // "others" per MFMA of the scheduling pipeline (0 = hipcc's own order)
-#endif
-#ifndef MVK_C3_SCHED2
-#define MVK_C3_SCHED2 2  // multiplier of MVK_C3_SCHED in the scaled-fp16 form (3 MFMAs per product instead of 6)
-#endif
-#ifndef MVK_C3_F16ACC
-// accumulators of the scaled-fp16 form: 2 = main + cross (dependent MFMAs on the same accumulator issue back to back),
-// 3 = one main + a cross per k-step of a pair, 4 = main + cross per k-step.  A/B (64 -> 64 @64x64, n = 128): 153 / 162 / 165 us
-#define MVK_C3_F16ACC 2
-#endif
-#ifndef MVK_C3_DIST
-// scaled-fp16 form: pairs of k-steps the A fragments are read ahead of their MFMAs (1 or 2).  A/B: 151 vs 167 us — the LDS
-// latency was not what the loop waits for, and 2 moves the barrier one pair up
-#define MVK_C3_DIST 1
-#endif
-#ifndef MVK_C3_NW2
-// waves per workgroup of the scaled-fp16 form: 4 = one per SIMD, 8 = two per SIMD with 72 weight registers each (twice the
-// tap split: 4 / 8 waves share a column tile).  A/B (64 -> 64 @64x64, n = 128, masked form): 157 vs 158 us, plain 129 vs 139 us
-// — what the second wave covers, the wider exchange and the 8-wave barrier (19 % of the cycles) take back.
-#define MVK_C3_NW2 4
-#endif
-#ifndef MVK_C3_BAR
-#define MVK_C3_BAR 7    // the pair behind which the tile's barrier sits (6: one more pair of cover for what follows it)
-#endif
-
 namespace mvk {
+
+constexpr int C3_SCHED = 4;   // "others" per MFMA of the scheduling pipeline of c3rs_kernel
+constexpr int C3_SCHED2 = 2;  // multiplier of C3_SCHED in the scaled-fp16 form (3 MFMAs per product instead of 6)
+constexpr int C3_BAR = 7;     // the pair behind which the tile's barrier sits
 
 #ifdef MVK_C3PROF  // tools/conv3_phase.py: per-wave cycle counters (total, waiting at the tile barrier)
 __device__ unsigned long long* g_c3_dbg = nullptr;
@@ -104,11 +76,10 @@ struct C3Cfg {
   static constexpr int KALL = 9 * CHUNKS;            // k-steps of one output element
   // The bf16 form needs 216 weight registers per wave: ONE wave per SIMD, every latency covered by software pipelining.  The
   // fp16 form has half the MFMAs (1730 cycles per tile) to hide the same staging / exchange / epilogue work behind, and that
-  // work alone takes 3260 cycles per tile (tools/conv3_phase.py, subtraction builds): the loop is bound by it, not by the
-  // matrix pipe.  MVK_C3_NW2 = 8 runs two waves per SIMD with 72 weight registers each; it measured no faster (see above).
-  static constexpr int NW = NP == 2 ? MVK_C3_NW2 : 4;  // waves per workgroup
-  static constexpr int KPW = 72 / NW;                // k-steps per wave: 18 = 216 (NP = 3) / 144 (NP = 2) weight registers, 9 = 72
-  static constexpr int HPP = KPW / 9;                // k-steps per loop iteration ("pair")
+  // work alone takes 3260 cycles per tile (subtraction builds): the loop is bound by it, not by the matrix pipe.
+  // Two waves per SIMD with 72 weight registers each measured no faster.
+  static constexpr int NW = 4;                       // waves per workgroup
+  static constexpr int KPW = 18;                     // k-steps per wave, two per loop iteration ("pair"): 216 (NP = 3) / 144 (NP = 2) weight registers
   static constexpr int KSPLIT = KALL / KPW;          // waves sharing one 32-column tile
   static constexpr int NCT = COUT / 32;
   static constexpr int ROLES = NCT * KSPLIT;
@@ -121,7 +92,7 @@ struct C3Cfg {
   static constexpr int PTAB_INTS = 16 * 32;
   // largest window reach (chunks) whose ring fits the LDS: 3 = W <= 94, 2 = W <= 62, 1 = W <= 30
   static constexpr int MAXD = CIN == 64 ? 3 : (NP == 2 ? 2 : 1);
-  static_assert(KALL % KPW == 0 && ROLES % NW == 0 && NW % KSPLIT == 0 && KPW % 9 == 0 && NF4 >= 1, "roles");
+  static_assert(KALL % KPW == 0 && ROLES % NW == 0 && NW % KSPLIT == 0 && NF4 >= 1, "roles");
   static_assert((S / 16) % 2 == 1, "odd 16-byte stride: conflict-free fragments");
   __host__ __device__ static constexpr int lds_bytes(int ring) { return ring * S + 2 * XBUF + PTAB_INTS * 4 + NW * 32 * 4; }
 };
@@ -146,13 +117,11 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
   int wgtype = blockIdx.x % T::WG_TYPES;
   int worker = blockIdx.x / T::WG_TYPES;
   const int workers = gridDim.x / T::WG_TYPES;
-#ifndef MVK_NO_XCDMAP
   if (T::WG_TYPES > 1 && gridDim.x % (8 * T::WG_TYPES) == 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     wgtype = slot % T::WG_TYPES;
     worker = xcd * (gridDim.x / (8 * T::WG_TYPES)) + slot / T::WG_TYPES;
   }
-#endif
   const int role = wgtype * T::NW + wave;
   const int ct = role / T::KSPLIT, ks = role % T::KSPLIT;
   const int ncol = ct * 32 + col;
@@ -194,8 +163,8 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
   const int H = g.H, W = g.W, W1 = W + 1, H1 = H + 1, PB = W1 * H1;
   const int dx32 = 32 % W1, dv32 = 32 / W1;
   const int D = g.D;
-  const int T0 = MVK_RFL((int)((long long)g.tiles * worker / workers));  // uniform trip count (see imgconv.hip)
-  const int T1 = MVK_RFL((int)((long long)g.tiles * (worker + 1) / workers));
+  const int T0 = __builtin_amdgcn_readfirstlane((int)((long long)g.tiles * worker / workers));  // uniform trip count (see imgconv.hip)
+  const int T1 = __builtin_amdgcn_readfirstlane((int)((long long)g.tiles * (worker + 1) / workers));
   const int NT = T1 - T0;
 
   // pixel-index table: entry [c & 15][l] = pixel index of position 32 c + l, or -1 (zero column / zero row / outside)
@@ -341,10 +310,10 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
         ab[j] = (int)s + kg * 16;
       }
     };
-    auto read_pair = [&](frag (&dst)[T::HPP][NP], const int (&ab)[NTAPW], int pr) {
+    auto read_pair = [&](frag (&dst)[2][NP], const int (&ab)[NTAPW], int pr) {
 #pragma unroll
-      for (int h = 0; h < T::HPP; ++h) {
-        const int gk = KSC * T::KPW + T::HPP * pr + h;
+      for (int h = 0; h < 2; ++h) {
+        const int gk = KSC * T::KPW + 2 * pr + h;
         const int j = gk / T::CHUNKS - TAP_LO, c = gk % T::CHUNKS;
 #pragma unroll
         for (int pc = 0; pc < NP; ++pc)
@@ -360,11 +329,11 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
     }
     const int wgrp = (wave / T::KSPLIT) * T::KSPLIT;  // first wave of this wave's column-tile group
 
-    // accumulators of a tile: NP = 3: one per k-step of a pair; NP = 2: main (hi hi') and cross (hi lo' + lo hi') per k-step
-    constexpr int NACC = NP == 3 ? 2 : MVK_C3_F16ACC;
-    f32x16 pend[NACC];
+    // accumulators of a tile: NP = 3: one per k-step of a pair; NP = 2: main (hi hi') and cross (hi lo' + lo hi'): dependent
+    // MFMAs on the same accumulator issue back to back
+    f32x16 pend[2];
 #pragma unroll
-    for (int i = 0; i < NACC; ++i) pend[i] = f32x16{0};
+    for (int i = 0; i < 2; ++i) pend[i] = f32x16{0};
     // msk / rr / pix of a tile are fetched (global loads) while the NEXT tile is multiplied and consumed one tile after
     // that: two register sets indexed by the compile-time parity of the tile, no copy between them (hipcc hoists a copy
     // "prev = cur" to the last use of prev, i.e. right behind the load, and waits there for the memory latency)
@@ -381,19 +350,9 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
       if constexpr (NP == 3) {
         sum = pend[0] + pend[1];
       } else {
-        f32x16 cross;
-        if constexpr (NACC == 4) {
-          cross = pend[2] + pend[3];
-          sum = pend[0] + pend[1];
-        } else if constexpr (NACC == 3) {
-          cross = pend[1] + pend[2];
-          sum = pend[0];
-        } else {
-          cross = pend[1];
-          sum = pend[0];
-        }
+        sum = pend[0];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sum[r] = fmaf(cross[r], 1.f / 2048.f, sum[r]);
+        for (int r = 0; r < 16; ++r) sum[r] = fmaf(pend[1][r], 1.f / 2048.f, sum[r]);
       }
 #pragma unroll
       for (int r = 0; r < T::KSPLIT; ++r) {
@@ -454,17 +413,14 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
     int tb = (int)(((long long)32 * T0) % RING) * T::S;  // first ring slot of tile T, in bytes
     int wch = (((T0 + D + 1) % NCH) + NCH) % NCH;       // ring chunk that chunk T+D+1 goes to
     int ab_cur[NTAPW], ab_nxt[NTAPW];
-    // A fragments are read DIST pairs ahead of their MFMAs (the bf16 form's 12 MFMAs per pair cover one burst of LDS reads of
-    // the four waves; the 6 of the fp16 form do not): set (pr + 9 P) % NSET holds pair pr of a tile of parity P
-    constexpr int DIST = NP == 2 ? MVK_C3_DIST : 1, NSET = DIST + 1;
+    // A fragments are read ONE pair ahead of their MFMAs: set (pr + P) % 2 holds pair pr of a tile of parity P
     // the barrier that publishes chunk T+D+1 must sit in front of the first read of tile T+1's fragments
-    constexpr int BAR = MVK_C3_BAR < 9 - DIST ? MVK_C3_BAR : 8 - DIST;
-    static_assert(18 % NSET == 0 && DIST >= 1, "the set of a pair must depend on the tile's parity only");
-    frag a_q[NSET][T::HPP][NP];
+    constexpr int BAR = C3_BAR;
+    static_assert(BAR < 8, "the next tile's first pair is read behind the barrier");
+    frag a_q[2][2][NP];
     if (NT > 0) {
       frag_base(ab_cur, tb);
-#pragma unroll
-      for (int dd = 0; dd < DIST; ++dd) read_pair(a_q[dd], ab_cur, dd);
+      read_pair(a_q[0], ab_cur, 0);
     }
     auto tile = [&](auto par_tag, int t) {
       constexpr int P = decltype(par_tag)::value;
@@ -474,21 +430,17 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
       const int wbase = wch * 32 * T::S;
       int tbn = tb + 32 * T::S;
       tbn = tbn >= (int)RINGB ? tbn - (int)RINGB : tbn;
-      f32x16 acc[NACC];
+      f32x16 acc[2];
 #pragma unroll
-      for (int i = 0; i < NACC; ++i) acc[i] = f32x16{0};
+      for (int i = 0; i < 2; ++i) acc[i] = f32x16{0};
       int upix[T::NF4];
 #pragma unroll
       for (int pr = 0; pr < 9; ++pr) {
-#ifndef MVK_C3X_NOFRAG  // MVK_C3X_*: subtraction experiments of tools/conv3_phase.py (timing only: the results are wrong)
-        if (pr + DIST <= 8) read_pair(a_q[(pr + DIST + 9 * P) % NSET], ab_cur, pr + DIST);
-        else read_pair(a_q[(pr + DIST + 9 * P) % NSET], ab_nxt, pr + DIST - 9);  // behind the barrier: the next tile's first pairs
-#endif
-        frag(&a_cur)[T::HPP][NP] = a_q[(pr + 9 * P) % NSET];
+        if (pr < 8) read_pair(a_q[(pr + 1 + P) % 2], ab_cur, pr + 1);
+        else read_pair(a_q[(pr + 1 + P) % 2], ab_nxt, 0);  // behind the barrier: the next tile's first pair
+        frag(&a_cur)[2][NP] = a_q[(pr + P) % 2];
         if (pr == 0) {
-#ifndef MVK_C3X_NOXCHG
           finish_pending(xb);
-#endif
           fetch_pix(P, (Tt - 1) & 15);            // table rows published by the previous barrier: ONE wait per tile
 #pragma unroll
           for (int k = 0; k < T::NF4; ++k) upix[k] = unit_pix(Tt + D + 2, k);
@@ -499,22 +451,17 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
         {
           constexpr int STEP = T::NF4 == 2 ? 3 : 2;
           constexpr int FIRST = BAR == 7 ? 1 : 0;  // the last conversion sits in front of the barrier
-#ifndef MVK_C3X_NOSTAGE
           if (pr >= FIRST && pr <= BAR && (pr - FIRST) % STEP == 0 && (pr - FIRST) / STEP < T::NF4) {
             write_unit(wbase, (pr - FIRST) / STEP);
             load_unit_at(upix[(pr - FIRST) / STEP], (pr - FIRST) / STEP);
           }
-#endif
         }
 #pragma unroll
         for (int o = 0; o < T::OWN; ++o) {
           if (o * 8 / T::OWN + 1 != pr) continue;
-#ifndef MVK_C3X_NOEPI
           fetch_row(P, o);                        // tile Tt-1: consumed two tiles later
           epilogue_row(P ^ 1, o, valid2);         // tile Tt-2
-#endif
         }
-#ifndef MVK_C3X_NOMFMA
         if constexpr (NP == 3) {
           constexpr int PA[6] = {0, 0, 1, 1, 0, 2}, PB_[6] = {2, 1, 0, 1, 0, 0};  // small terms first
 #pragma unroll
@@ -522,28 +469,17 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][PA[m]], Bw[2 * pr][PB_[m]], acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][PA[m]], Bw[2 * pr + 1][PB_[m]], acc[1], 0, 0, 0);
           }
-        } else if constexpr (T::HPP == 1) {  // one k-step per iteration (two waves per SIMD): main, cross
-          static_assert(NACC == 2, "two accumulators");
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[pr][1], acc[1], 0, 0, 0);
-          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[pr][0], acc[0], 0, 0, 0);
-          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][1], Bw[pr][0], acc[1], 0, 0, 0);
-        } else {  // cross terms (pieces 0 x 1, 1 x 0) and the main term in accumulators of their own
-          constexpr int M0 = 0, M1 = NACC == 4 ? 1 : 0, C0 = NACC == 4 ? 2 : 1, C1 = NACC == 4 ? 3 : (NACC == 3 ? 2 : 1);
-          acc[C0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[2 * pr][1], acc[C0], 0, 0, 0);
-          acc[M0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[2 * pr][0], acc[M0], 0, 0, 0);
-          acc[C1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], Bw[2 * pr + 1][1], acc[C1], 0, 0, 0);
-          acc[M1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], Bw[2 * pr + 1][0], acc[M1], 0, 0, 0);
-          acc[C0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][1], Bw[2 * pr][0], acc[C0], 0, 0, 0);
-          acc[C1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][1], Bw[2 * pr + 1][0], acc[C1], 0, 0, 0);
+        } else {  // the main term (acc[0]) and the cross terms (pieces 0 x 1, 1 x 0: acc[1]) in accumulators of their own
+          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[2 * pr][1], acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][0], Bw[2 * pr][0], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], Bw[2 * pr + 1][1], acc[1], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][0], Bw[2 * pr + 1][0], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[0][1], Bw[2 * pr][0], acc[1], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[1][1], Bw[2 * pr + 1][0], acc[1], 0, 0, 0);
         }
-#else
-        acc[0][pr] += __builtin_bit_cast(f32x4, a_cur[0][0])[0] + __builtin_bit_cast(f32x4, a_cur[T::HPP - 1][NP - 1])[1];
-#endif
-#ifndef MVK_C3X_NOXCHG
         if (pr == BAR + 1) gather_result(xb);  // behind the barrier: result of tile Tt-1
-#endif
-        if (MVK_C3_SCHED > 0 && T::NW == 4) {  // the same "other" work per pair behind half as many MFMAs in the fp16 form
-          constexpr int OTHERS = (MVK_C3_SCHED > 0 ? MVK_C3_SCHED : 1) * (NP == 3 ? 1 : MVK_C3_SCHED2);
+        {  // "1 MFMA, N others": the same "other" work per pair behind half as many MFMAs in the fp16 form
+          constexpr int OTHERS = C3_SCHED * (NP == 3 ? 1 : C3_SCHED2);
 #pragma unroll
           for (int m = 0; m < 4 * NP; ++m) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -561,7 +497,7 @@ __device__ __forceinline__ void c3rs_body(const C3Args& g) {
 #endif
       }
 #pragma unroll
-      for (int i = 0; i < NACC; ++i) pend[i] = acc[i];
+      for (int i = 0; i < 2; ++i) pend[i] = acc[i];
       rotate();
 #pragma unroll
       for (int j = 0; j < NTAPW; ++j) ab_cur[j] = ab_nxt[j];
@@ -704,13 +640,9 @@ struct C3WArgs {
   const float* y_amax;
 };
 
-#ifndef MVK_C3W_PAD
-#define MVK_C3W_PAD 16
-#endif
-#ifndef MVK_C3W_SCHED
-#define MVK_C3W_SCHED 4
-#endif
-constexpr int C3W_S = 6 * 64 + MVK_C3W_PAD;  // bytes per slot: 3 pieces x 64 channels bf16 + pad
+constexpr int C3W_PAD = 16;               // pad bytes per slot
+constexpr int C3W_SCHED = 4;              // "others" per MFMA of the weight gradient's scheduling pipeline (bf16 form only, see below)
+constexpr int C3W_S = 6 * 64 + C3W_PAD;   // bytes per slot: 3 pieces x 64 channels bf16 + pad
 static int c3w_lds_bytes(int ring) { return (ring + 64) * C3W_S + 16 * 32 * 4; }
 
 typedef __bf16 c3_bf16x4 __attribute__((ext_vector_type(4)));
@@ -752,13 +684,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int wgtype = blockIdx.x % types;
   int worker = blockIdx.x / types;
   const int workers = gridDim.x / types;
-#ifndef MVK_NO_XCDMAP
   if (types > 1 && gridDim.x % (8 * types) == 0) {  // the types of a worker on one XCD (imgconv.hip)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     wgtype = slot % types;
     worker = xcd * (gridDim.x / (8 * types)) + slot / types;
   }
-#endif
   const int ci0 = (wgtype % cit) * 64, co0 = (wgtype / cit) * 64;
   const int h = wave & 1, c = wave >> 1;  // this wave's 32-channel tiles of the block
 
@@ -770,8 +700,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int H = g.H, W = g.W, W1 = W + 1, H1 = H + 1, PB = W1 * H1;
   const int dx32 = 32 % W1, dv32 = 32 / W1;
   const int D = g.D;
-  const int T0 = MVK_RFL((int)((long long)g.tiles * worker / workers));  // uniform trip count (see imgconv.hip)
-  const int T1 = MVK_RFL((int)((long long)g.tiles * (worker + 1) / workers));
+  const int T0 = __builtin_amdgcn_readfirstlane((int)((long long)g.tiles * worker / workers));  // uniform trip count (see imgconv.hip)
+  const int T1 = __builtin_amdgcn_readfirstlane((int)((long long)g.tiles * (worker + 1) / workers));
   const int NT = T1 - T0;
 
   int pimg, pv, px;
@@ -998,11 +928,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       // the "1 MFMA, N others" directive pays in the bf16 form only: the fp16 form (half the MFMAs per step) measured 174-182 us
       // with it and 158-166 us with hipcc's own order (64 x 64 @64x64, n = 128, incl. the finish); the bf16 form 214 vs 231
-      if (MVK_C3W_SCHED > 0 && NP == 3) {
+      if (NP == 3) {
 #pragma unroll
         for (int m = 0; m < 6 * NP; ++m) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x496, MVK_C3W_SCHED > 0 ? MVK_C3W_SCHED : 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x496, C3W_SCHED, 0);
         }
       }
 #pragma unroll

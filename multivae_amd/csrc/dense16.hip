@@ -203,9 +203,11 @@ __global__ __launch_bounds__(256) void d16_first_kernel(const D16First g) {
 // LDS stages, one barrier per k-tile; the next tile's global loads are issued before the MFMAs of the current one.
 // ---------------------------------------------------------------------------------------------------------------------
 enum { D16_NLL = 0, D16_BWD = 1 };
-#ifndef D16_NT128_OCC
-#define D16_NT128_OCC 1  // workgroups per CU of the 128-row tile (its two register sets put it above 256 registers)
-#endif
+constexpr int D16_OCC_128 = 1;  // workgroups per CU of the 128-row tile (its two register sets put it above 256 registers)
+// Occupancy bound of the 64-row forms.  4 = at most 128 registers, so that a wave of the backward-data form fits beside a
+// register-stationary one (imgconv DOWN forms hold 348-368 of a SIMD's 512 registers; this kernel's 173 do not fit and its launch
+// waits for theirs to end): measured, it DOES run beside them then — with 87 spilled registers, 227 us instead of 36, step +9 %.
+constexpr int D16_OCC_64 = 2;
 
 // (mvk_fast_sigmoid: common.hpp)
 #define d16_sigmoid mvk_fast_sigmoid
@@ -235,15 +237,7 @@ struct D16Nt {
 };
 
 template <int BM, int EPI>
-#ifndef D16_NT64_BWD_OCC
-#define D16_NT64_BWD_OCC 2  // occupancy bound of the 64-row backward-data form.  4 = at most 128 registers, so that a wave fits beside a
-// register-stationary one (imgconv DOWN forms hold 348-368 of a SIMD's 512 registers; this kernel's 173 do not fit and its launch
-// waits for theirs to end): measured, it DOES run beside them then — with 87 spilled registers, 227 us instead of 36, step +9 %.
-#endif
-#ifndef D16_NT64_FWD_OCC
-#define D16_NT64_FWD_OCC 2
-#endif
-__global__ __launch_bounds__(256, BM == 64 ? (EPI == 1 ? D16_NT64_BWD_OCC : D16_NT64_FWD_OCC) : D16_NT128_OCC) void d16_nt_kernel(const D16Nt g) {
+__global__ __launch_bounds__(256, BM == 64 ? D16_OCC_64 : D16_OCC_128) void d16_nt_kernel(const D16Nt g) {
   constexpr int BN = 128, TM = BM / 64, TN = 2;
   constexpr int APL = BM * 64, BPL = BN * 64;  // bytes per plane tile
   constexpr int STAGE = 2 * APL + 2 * BPL;
@@ -276,19 +270,11 @@ __global__ __launch_bounds__(256, BM == 64 ? (EPI == 1 ? D16_NT64_BWD_OCC : D16_
     b_kmax[u] = (n0 + row < g.N) ? K - oct * 8 : 0;
   }
   // two register sets: a k-tile's loads are issued two iterations before its LDS write (one iteration = the MFMAs of one k-tile
-  // is shorter than the latency of an L2 miss: with one set every iteration waited for its loads)
+  // is shorter than the latency of an L2 miss: with one set every iteration waited for its loads).  One set for the 64-row forms
+  // (173 -> 149 registers) was measured and retired: DESIGN.md §9.
   struct Raw {
     u32x4 ah[NA], al[NA], bh[NB], bl[NB];
   };
-#ifndef D16_BWD_ONESET
-#define D16_BWD_ONESET 0  // 1: the 64-row backward-data form loads ONE k-tile ahead (one register set: 173 -> 149 registers, no spills).
-// It then fits beside imgconv<DOWN, 4, 64, 128> (352 + 152) and runs there: 106 -> 133 us while that launch goes 106 -> 130 us,
-// step +0.7 % (four same-box pairs).  Two MFMA-heavy kernels on one SIMD share a power-limited matrix pipe: co-residency is zero-sum.
-#endif
-#ifndef D16_FWD_ONESET
-#define D16_FWD_ONESET 0  // the same for the 64-row forward form (fused tail)
-#endif
-  constexpr bool ONESET = BM == 64 && ((EPI == 1 && D16_BWD_ONESET) || (EPI == 0 && D16_FWD_ONESET));
   Raw R0, R1;
   auto sel = [](bool ok, int off) { return __builtin_unpredictable(ok) ? off : 0x7fffffff; };  // out of range = zero fill
   auto gload = [&](Raw& r, int k0) {
@@ -371,29 +357,14 @@ __global__ __launch_bounds__(256, BM == 64 ? (EPI == 1 ? D16_NT64_BWD_OCC : D16_
   const unsigned long long tk0 = (g.dbg & 16) ? __builtin_readcyclecounter() : 0ull;
   gload(R0, 0);
   lwrite(R0, lds);
-  if (ONESET) {
-    gload(R0, 32);
-  } else {
-    gload(R1, 32);
-    gload(R0, 64);
-  }
+  gload(R1, 32);
+  gload(R0, 64);
   __syncthreads();
   rfrag(FA, lds, 0);
   // one k-tile: LDS stage `cur` is multiplied; tile t+1 goes from `rw` to stage `nxt`, then tile t+3 is fetched into `rw`
-#ifndef D16_ONEFRAG
-#define D16_ONEFRAG 0  // 1 (with ONESET): ONE fragment set, read where it is used — 24 registers less, for 4 waves per SIMD (A/B)
-#endif
   auto ktile = [&](int t, const char* cur, char* nxt, Raw& rw) {
     lwrite(rw, nxt);               // tile t+1 (the last readers of `nxt` passed the barrier of iteration t-1)
-    gload(rw, (t + (ONESET ? 2 : 3)) * 32);  // past the end of K: out of range, zero fill, no traffic
-    if (D16_ONEFRAG && ONESET) {
-      rfrag(FA, cur, 0);
-      mfmas(FA);
-      rfrag(FA, cur, 1);
-      mfmas(FA);
-      __syncthreads();
-      return;
-    }
+    gload(rw, (t + 3) * 32);       // past the end of K: out of range, zero fill, no traffic
     rfrag(FB, cur, 1);
     mfmas(FA);
     D16_INTERLEAVE(2)
@@ -403,7 +374,7 @@ __global__ __launch_bounds__(256, BM == 64 ? (EPI == 1 ? D16_NT64_BWD_OCC : D16_
     D16_INTERLEAVE(1)
   };
   for (int t = 0; t < nt; t += 2) {  // an odd nt runs one k-tile of zeros (zero-filled loads)
-    ktile(t, lds, lds + STAGE, ONESET ? R0 : R1);
+    ktile(t, lds, lds + STAGE, R1);
     ktile(t + 1, lds + STAGE, lds, R0);
   }
 

@@ -311,15 +311,10 @@ static int try_launch_fast(const GemmDesc& d, int zdim, hipStream_t s) {
 
 static unsigned long long* g_dbg = nullptr;
 static int g_dbg_flags = 0;
-// Measurement hooks (declared in mvk.h): only experiment builds (-DMVK_PHASES / -DMVK_EXPER, tools/build_exper.sh,
-// tools/build_variants.sh) read what they set; in the shipped library they are inert.
+// Measurement hooks (declared in mvk.h).  Only a -DMVK_PHASES build reads the phase buffer; the flags are the host-side dispatch
+// bits below (0x100 / 0x200 / 0x400 / 0x800) in every build.
 extern "C" void mvk_debug_set_phase_buffer(unsigned long long* p) { g_dbg = p; }
-extern "C" void mvk_debug_set_flags(int f) {
-  g_dbg_flags = f;
-#ifdef MVK_EXPER
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bf_flags), &f, sizeof(int));
-#endif
-}
+extern "C" void mvk_debug_set_flags(int f) { g_dbg_flags = f; }
 
 int launch_igemm(const GemmDesc& d_in, int zdim, hipStream_t s, LaunchInfo* info) {
   GemmDesc d = d_in;

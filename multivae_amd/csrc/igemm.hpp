@@ -75,9 +75,7 @@ struct GemmDesc {
   int dbg_flags;            // experiment switches (debug builds only)
 };
 
-#ifndef MVK_MIN_WAVES
-#define MVK_MIN_WAVES 3
-#endif
+constexpr int MIN_WAVES = 3;  // occupancy bound (waves per SIMD) of the fp32 tiled kernels
 constexpr int BK = 16;
 
 template <int BM, int BN>
@@ -341,7 +339,7 @@ __device__ __forceinline__ bool run_epilogue_vec(const GemmDesc& d, f32x16 (&acc
 }
 
 template <int BM, int BN>
-__global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_kernel(const GemmDesc d) {
+__global__ __launch_bounds__(256, MIN_WAVES) void igemm_kernel(const GemmDesc d) {
   using T = TileCfg<BM, BN>;
   __shared__ __attribute__((aligned(16))) float lds[2 * BK * (T::SA + T::SB)];
   float* As = lds;                    // [2][BK][SA]

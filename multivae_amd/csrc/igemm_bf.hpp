@@ -20,11 +20,9 @@
 #include "bf3.hpp"
 #include "igemm_fast.hpp"
 
-#ifndef MVK_BF_OCC_SMALL
-#define MVK_BF_OCC_SMALL 3  // 4 (<= 128 VGPRs) spills 92-240 bytes per lane in every 128x32 variant
-#endif
 namespace mvk {
 
+constexpr int BF_OCC_SMALL = 3;  // occupancy bound of the 128x32 tiles: 4 (<= 128 VGPRs) spills 92-240 bytes per lane in every variant
 
 template <int BM, int BN>
 struct BfCfg {
@@ -48,18 +46,7 @@ struct BfCfg {
 };
 
 // two fp32 values -> three dwords, each holding the (lo = x, hi = y) pair of one bf16 piece
-#ifdef MVK_EXPER
-__device__ int g_bf_flags;
-#endif
 __device__ __forceinline__ void bf_split3(float x, float y, unsigned& p0, unsigned& p1, unsigned& p2) {
-#ifdef MVK_EXPER
-  if (g_bf_flags & 1) {  // experiment: no conversion arithmetic
-    p0 = __builtin_amdgcn_perm(__float_as_uint(y), __float_as_uint(x), 0x07060302u);
-    p1 = p0;
-    p2 = p0;
-    return;
-  }
-#endif
   // scalar subtractions on purpose (built with -fno-slp-vectorize): v_pk_add_f32 needs aligned register pairs,
   // which costs copies of freshly loaded registers (and the waits that go with them) beside the MFMAs
   const bf16x2 a0 = __builtin_convertvector(f32x2{x, y}, bf16x2);
@@ -290,33 +277,7 @@ __device__ __forceinline__ void igemm_bf_body(const GemmDesc& d, const unsigned 
 
   auto load_tiles = [&](int k0, u32x4 (&ra)[NRA], u32x4 (&ya)[NYA], u32x4 (&rb)[T::NB4]) {
     auto sel = [](bool ok, int off) { return __builtin_unpredictable(ok) ? off : 0x7fffffff; };  // keep it a v_cndmask
-#ifdef MVK_EXPER
-    if (d.dbg_flags & 2) {  // experiment: no global traffic
-      for (int u = 0; u < NRA; ++u) ra[u] = u32x4{1, 2, 3, 4};
-      for (int u = 0; u < T::NB4; ++u) rb[u] = u32x4{1, 2, 3, 4};
-      return;
-    }
-    const bool skip_a = d.dbg_flags & 64, skip_b = d.dbg_flags & 128;
-    if (skip_a) for (int u = 0; u < NRA; ++u) ra[u] = u32x4{1, 2, 3, 4};
-    if (skip_b) for (int u = 0; u < T::NB4; ++u) rb[u] = u32x4{1, 2, 3, 4};
-#elif defined(MVK_X_NOA) || defined(MVK_X_NOB)  // compile-time experiments (tools/build_variants.sh): schedule undisturbed
-#ifdef MVK_X_NOA
-    constexpr bool skip_a = true;
-    for (int u = 0; u < NRA; ++u) ra[u] = u32x4{1, 2, 3, 4};
-#else
-    constexpr bool skip_a = false;
-#endif
-#ifdef MVK_X_NOB
-    constexpr bool skip_b = true;
-    for (int u = 0; u < T::NB4; ++u) rb[u] = u32x4{1, 2, 3, 4};
-#else
-    constexpr bool skip_b = false;
-#endif
-#else
-    constexpr bool skip_a = false, skip_b = false;
-#endif
-    if (skip_a) {
-    } else if (AMODE == AM_PLAIN_K) {
+    if (AMODE == AM_PLAIN_K) {
 #pragma unroll
       for (int u = 0; u < T::NA4; ++u) {
         const int idx = tid + u * 256;
@@ -404,8 +365,7 @@ __device__ __forceinline__ void igemm_bf_body(const GemmDesc& d, const unsigned 
         }
       }
     }
-    if (skip_b) {
-    } else if (BMODE == BM_K) {
+    if (BMODE == BM_K) {
 #pragma unroll
       for (int u = 0; u < T::NB4; ++u) {
         const int idx = tid + u * 256;
@@ -471,79 +431,58 @@ __device__ __forceinline__ void igemm_bf_body(const GemmDesc& d, const unsigned 
 #ifdef MVK_PHASES
     unsigned long long tlast = __builtin_readcyclecounter();
 #endif
-#ifdef MVK_EXPER
-    const bool no_mfma = d.dbg_flags & 32, no_write = d.dbg_flags & 16;
-#else
-    constexpr bool no_mfma = false, no_write = false;
-#endif
     constexpr int PA[6] = {0, 1, 2, 0, 1, 0};  // smallest terms first
     constexpr int PB[6] = {2, 1, 0, 1, 0, 0};
     if (T::TM * T::TN == 1) {
       // one MFMA tile per wave: alternate the two k-steps on two accumulators so consecutive MFMAs are independent
       bf16x8 af[2][3], bfr[2][3];
-      if (!no_mfma) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
+      for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            af[ks][p] = *reinterpret_cast<const bf16x8*>(a_frag + p * T::A_PIECE + ks * 32);
-            bfr[ks][p] = *reinterpret_cast<const bf16x8*>(b_frag + p * T::B_PIECE + ks * 32);
-          }
-      }
+        for (int p = 0; p < 3; ++p) {
+          af[ks][p] = *reinterpret_cast<const bf16x8*>(a_frag + p * T::A_PIECE + ks * 32);
+          bfr[ks][p] = *reinterpret_cast<const bf16x8*>(b_frag + p * T::B_PIECE + ks * 32);
+        }
 #pragma unroll
       for (int q = 0; q < 6; ++q)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-          if (!no_mfma) {
-            if (ks == 0) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][PA[q]], bfr[0][PB[q]], acc[0][0], 0, 0, 0);
-            else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][PA[q]], bfr[1][PB[q]], acc2, 0, 0, 0);
-          }
+          if (ks == 0) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][PA[q]], bfr[0][PB[q]], acc[0][0], 0, 0, 0);
+          else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][PA[q]], bfr[1][PB[q]], acc2, 0, 0, 0);
           const int slot = q * 2 + ks;
-          if (!no_write) convert_range(slot * NPAIR / NSLOT, (slot + 1) * NPAIR / NSLOT, ra, ya, rb);
+          convert_range(slot * NPAIR / NSLOT, (slot + 1) * NPAIR / NSLOT, ra, ya, rb);
         }
     } else {
 #pragma unroll
       for (int ks = 0; ks < BKT / 16; ++ks) {
         bf16x8 af[T::TM][3], bfr[T::TN][3];
-        if (!no_mfma) {
+#pragma unroll
+        for (int a = 0; a < T::TM; ++a)
+#pragma unroll
+          for (int p = 0; p < 3; ++p)
+            af[a][p] = *reinterpret_cast<const bf16x8*>(a_frag + p * T::A_PIECE + a * 8 * 80 + ks * 32);
+#pragma unroll
+        for (int b = 0; b < T::TN; ++b)
+#pragma unroll
+          for (int p = 0; p < 3; ++p)
+            bfr[b][p] = *reinterpret_cast<const bf16x8*>(b_frag + p * T::B_PIECE + b * 8 * 80 + ks * 32);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
 #pragma unroll
           for (int a = 0; a < T::TM; ++a)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-              af[a][p] = *reinterpret_cast<const bf16x8*>(a_frag + p * T::A_PIECE + a * 8 * 80 + ks * 32);
-#pragma unroll
-          for (int b = 0; b < T::TN; ++b)
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-              bfr[b][p] = *reinterpret_cast<const bf16x8*>(b_frag + p * T::B_PIECE + b * 8 * 80 + ks * 32);
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-          if (!no_mfma) {
-#pragma unroll
-            for (int a = 0; a < T::TM; ++a)
-#pragma unroll
-              for (int b = 0; b < T::TN; ++b)
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][PA[q]], bfr[b][PB[q]], acc[a][b], 0, 0, 0);
-          }
+            for (int b = 0; b < T::TN; ++b)
+              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][PA[q]], bfr[b][PB[q]], acc[a][b], 0, 0, 0);
           const int slot = ks * 6 + q;
-          if (!no_write) convert_range(slot * NPAIR / NSLOT, (slot + 1) * NPAIR / NSLOT, ra, ya, rb);
+          convert_range(slot * NPAIR / NSLOT, (slot + 1) * NPAIR / NSLOT, ra, ya, rb);
         }
       }
     }
     MVK_T(0)
     __syncthreads();  // every wave is done reading the tile
     MVK_T(1)
-    if (!no_write) write_pieces(ra);
+    write_pieces(ra);
     MVK_T(2)
-#ifdef MVK_EXPER
-    if (no_write) {  // keep the loads alive
-      unsigned s_ = 0;
-      for (int u = 0; u < T::NA4; ++u) s_ += ra[u].x ^ ra[u].y ^ ra[u].z ^ ra[u].w;
-      for (int u = 0; u < T::NB4; ++u) s_ += rb[u].x ^ rb[u].y ^ rb[u].z ^ rb[u].w;
-      if (s_ == 0x12345677u) As[tid] = 1;
-    }
-#endif
     __syncthreads();
     MVK_T(3)
   };
@@ -584,7 +523,7 @@ __device__ __forceinline__ void igemm_bf_body(const GemmDesc& d, const unsigned 
 }
 
 template <int BM, int BN, int AMODE, int BMODE, bool AACT, int DEPTH>
-__global__ __launch_bounds__(256, (BM * BN <= 128 * 32) ? MVK_BF_OCC_SMALL : ((BM * BN <= 128 * 64) ? 3 : 2)) void igemm_bf_kernel(const GemmDesc d) {
+__global__ __launch_bounds__(256, (BM * BN <= 128 * 32) ? BF_OCC_SMALL : ((BM * BN <= 128 * 64) ? 3 : 2)) void igemm_bf_kernel(const GemmDesc d) {
   igemm_bf_body<BM, BN, AMODE, BMODE, AACT, DEPTH>(d, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
@@ -592,7 +531,7 @@ __global__ __launch_bounds__(256, (BM * BN <= 128 * 32) ? MVK_BF_OCC_SMALL : ((B
 // convolutional encoder at the training batch: 256 workgroups each, two dependent launches of ~35 us on the step's last chain;
 // three workgroups fit a CU, so one grid of 512 runs them side by side).  grid.x = n0 + n1 workgroups; the first n0 belong to d0.
 template <int BM, int BN, int AMODE, int BMODE, bool AACT, int DEPTH>
-__global__ __launch_bounds__(256, (BM * BN <= 128 * 32) ? MVK_BF_OCC_SMALL : ((BM * BN <= 128 * 64) ? 3 : 2)) void igemm_bf_pair_kernel(
+__global__ __launch_bounds__(256, (BM * BN <= 128 * 32) ? BF_OCC_SMALL : ((BM * BN <= 128 * 64) ? 3 : 2)) void igemm_bf_pair_kernel(
     const GemmDesc d0, const GemmDesc d1, const unsigned n0, const unsigned gx0, const unsigned gy0, const unsigned gx1,
     const unsigned gy1) {
   unsigned b = blockIdx.x;

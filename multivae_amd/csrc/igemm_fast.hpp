@@ -37,7 +37,7 @@ struct FastCfg {
 };
 
 template <int BM, int BN, int BKT, int AMODE, int BMODE, bool AACT>
-__global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const GemmDesc d) {
+__global__ __launch_bounds__(256, MIN_WAVES) void igemm_fast_kernel(const GemmDesc d) {
   using T = FastCfg<BM, BN, BKT, (AMODE == AM_PLAIN_K || AMODE == AM_ROW), (BMODE == BM_K)>;
   __shared__ __attribute__((aligned(16))) float lds[2 * BKT * (T::SA + T::SB) + 8];
   float* As = lds;
@@ -141,12 +141,6 @@ __global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const Ge
   // global -> registers (no dependent use: the loads stay in flight across the MFMAs)
   // ------------------------------------------------------------------------------------------------
   auto load_tiles = [&](int k0) {
-#if defined(MVK_PHASES) || defined(MVK_EXPER)
-    if (d.dbg_flags & 1) {  // experiment: no A traffic
-      for (int u = 0; u < T::NA4; ++u) ra[u] = u32x4{0, 0, 0, 0};
-      goto load_b_only;
-    }
-#endif
     if (AMODE == AM_PLAIN_K) {
 #pragma unroll
       for (int u = 0; u < T::NA4; ++u) {
@@ -185,12 +179,7 @@ __global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const Ge
         const int kq = (idx % (BKT / 4)) * 4;
         const int hh = mul * pb[u] + dh, ww = mul * pc[u] + dw;
         const bool ok = pa[u] >= 0 && (k0 + kq) < kend && hh >= 0 && hh < A.H && ww >= 0 && ww < A.W;
-#if defined(MVK_PHASES) || defined(MVK_EXPER)
-        const int img = (d.dbg_flags & 4) ? (pa[u] & 7) : pa[u];  // experiment: all blocks read 8 images (cache hits)
-#else
-        const int img = pa[u];
-#endif
-        const int off = ok ? (((img * A.H + hh) * A.W + ww) * A.C + c0 + kq) * 4 : OOB;
+        const int off = ok ? (((pa[u] * A.H + hh) * A.W + ww) * A.C + c0 + kq) * 4 : OOB;
         ra[u] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0);
       }
     } else {  // AM_COL: rows = (tap, channel), k = position
@@ -218,13 +207,6 @@ __global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const Ge
         ra[u] = __builtin_amdgcn_raw_buffer_load_b128(rsA, off, 0, 0);
       }
     }
-#if defined(MVK_PHASES) || defined(MVK_EXPER)
-  load_b_only:
-    if (d.dbg_flags & 2) {  // experiment: no B traffic
-      for (int u = 0; u < T::NB4; ++u) rb[u] = u32x4{0, 0, 0, 0};
-      return;
-    }
-#endif
     if (BMODE == BM_K) {
 #pragma unroll
       for (int u = 0; u < T::NB4; ++u) {
@@ -246,9 +228,6 @@ __global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const Ge
   // registers -> LDS (k-major tiles)
   // ------------------------------------------------------------------------------------------------
   auto store_tiles = [&](int buf) {
-#if defined(MVK_PHASES) || defined(MVK_EXPER)
-    if (d.dbg_flags & 16) return;  // experiment: no LDS writes
-#endif
     float* da = As + buf * BKT * T::SA;
     float* db = Bs + buf * BKT * T::SB;
 #pragma unroll
@@ -349,14 +328,6 @@ __global__ __launch_bounds__(256, MVK_MIN_WAVES) void igemm_fast_kernel(const Ge
     unsigned long long te = __builtin_readcyclecounter();
     atomicAdd(d.dbg + 6, te - tk0);
     atomicAdd(d.dbg + 7, 1ull);
-  }
-#endif
-#if defined(MVK_PHASES) || defined(MVK_EXPER)
-  if (d.dbg_flags & 8) {  // experiment: no epilogue (keep the accumulators alive)
-    float s = 0.f;
-    for (int a = 0; a < T::TM; ++a) for (int b = 0; b < T::TN; ++b) for (int r = 0; r < 16; ++r) s += acc[a][b][r];
-    if (s == 12345.678f) d.e.out[0] = s;
-    return;
   }
 #endif
   if (run_epilogue_vec<T, BM, BN, 2 * BKT * (T::SA + T::SB)>(d, acc, lds, tid, m0, n0, wm, wn, l31, lhi, ph, pw)) return;

@@ -31,24 +31,13 @@
 
 #include "bf3.hpp"
 
-#ifndef MVK_IC_ABL
-#define MVK_IC_ABL 0  // subtraction builds (tools/ab_probe.sh): 1 = every input load from the worker's first unit (L2-resident), 2 = every store and mask load on the first unit
-#endif
-#ifdef MVK_NO_RFL
-#define MVK_RFL(x) (x)
-#else
-#define MVK_RFL(x) __builtin_amdgcn_readfirstlane(x)
-#endif
-
-#ifndef MVK_IC_SCHED
-#define MVK_IC_SCHED (HS == 8 ? 5 : 4)  // "others" per MFMA of the scheduling pipeline in imgconv_kernel (0 = hipcc's own order)
-#endif
-
-#ifndef MVK_IC_SCHED2
-#define MVK_IC_SCHED2 2  // multiplier of MVK_IC_SCHED in the scaled-fp16 form (half the MFMAs per pair of k-steps)
-#endif
 
 namespace mvk {
+
+// "others" per MFMA of the scheduling pipeline in imgconv_kernel, and its multiplier in the scaled-fp16 form (half the MFMAs
+// per pair of k-steps)
+constexpr int ic_sched(int hs) { return hs == 8 ? 5 : 4; }
+constexpr int IC_SCHED2 = 2;
 
 #ifdef MVK_ICPROF  // tools/imgconv_phase.py: per-wave cycle counters (total, waiting at the tile barrier, k-loops)
 __device__ unsigned long long* g_ic_dbg = nullptr;
@@ -150,13 +139,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int wgtype = blockIdx.x % T::WG_TYPES;
   int worker = blockIdx.x / T::WG_TYPES;
   const int workers = gridDim.x / T::WG_TYPES;
-#ifndef MVK_NO_XCDMAP
   if (T::WG_TYPES > 1 && gridDim.x % (8 * T::WG_TYPES) == 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     wgtype = slot % T::WG_TYPES;
     worker = xcd * (gridDim.x / (8 * T::WG_TYPES)) + slot / T::WG_TYPES;
   }
-#endif
 
   // ---- role of this wave ----------------------------------------------------------------------------------
   int cls = 0, ct = 0, ks = 0;
@@ -280,12 +267,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const long long units = g.n / T::SU;
   // readfirstlane: the 64-bit division is emitted on the vector ALU, which makes the trip count of the unit loop 'divergent'
   // for hipcc (exec-masked loop, every live-out accumulator read back per iteration: 32 v_accvgpr_read + a drain of the matrix pipe per tile)
-  const long long u0 = MVK_RFL((int)(units * worker / workers));
-  const long long u1 = MVK_RFL((int)(units * (worker + 1) / workers));
+  const long long u0 = __builtin_amdgcn_readfirstlane((int)(units * worker / workers));
+  const long long u1 = __builtin_amdgcn_readfirstlane((int)(units * (worker + 1) / workers));
 
   f32x4 raw[T::NF4];
   auto unit_src = [&](long long u) {  // clamped: the tail re-reads the last unit instead of branching
-    const long long uc = (MVK_IC_ABL & 1) ? u0 : (u < u1 ? u : u1 - 1);
+    const long long uc = u < u1 ? u : u1 - 1;
     return reinterpret_cast<const f32x4*>(g.A + uc * IN_UNIT) + tid;
   };
   auto write_f4 = [&](char* buf, int k) {
@@ -347,8 +334,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // A fragments are read ahead of their MFMAs: one pair of k-steps in the bf16 form (12 MFMAs = 384 matrix-pipe cycles cover a
   // ds_read_b128 under load), TWO pairs in the fp16 form, whose pair is 6 MFMAs = 192 cycles — less than the latency of an LDS
   // read when the four waves of the workgroup issue their reads together (the LDS array is busy 8 cycles per b128 wave read,
-  // 16 reads per pair).  Subtraction builds (MVK_IC_ABL: all loads and stores on one L2-resident unit) run at 0.9 of the full
-  // kernel's time: the loop waits on neither HBM nor the instruction count (r04: -10 % instructions, same time).
+  // 16 reads per pair).  Subtraction builds (all loads and stores on one L2-resident unit) ran at 0.9 of the full kernel's
+  // time: the loop waits on neither HBM nor the instruction count (r04: -10 % instructions, same time).
 #ifndef MVK_IC_DEPTH2
 #define MVK_IC_DEPTH2 0  // measured: no gain alone (65-80 us either way), +3 % on the step
 #endif
@@ -432,8 +419,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       const char* const abuf = lds + cur * T::BUF;
       char* const nbuf = lds + (cur ^ 1) * T::BUF;
       const f32x4* const src2 = unit_src(u + 2);
-      float* const outp_cur = g.out + ((MVK_IC_ABL & 2) ? u0 + 2 : u) * OUT_UNIT;
-      const float* const srcp_cur = HAS_SRC ? g.act_src + ((MVK_IC_ABL & 2) ? u0 + 2 : u) * OUT_UNIT : nullptr;
+      float* const outp_cur = g.out + u * OUT_UNIT;
+      const float* const srcp_cur = HAS_SRC ? g.act_src + u * OUT_UNIT : nullptr;
 #pragma unroll
       for (int tt = 0; tt < T::TPU; ++tt) {
         const int ptt1 = (tt + T::TPU - 1) % T::TPU;          // tile-in-unit index of tile T-1
@@ -529,11 +516,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 a_cur[h][pc] = a_nxt[h][pc];
               }
             }
-          if (MVK_IC_SCHED > 0) {  // "1 MFMA, N others" (see the one-tile-latency loop)
+          {  // "1 MFMA, N others" (see the one-tile-latency loop)
 #pragma unroll
             for (int m = 0; m < 4 * NP; ++m) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-              __builtin_amdgcn_sched_group_barrier(0x496, (MVK_IC_SCHED > 0 ? MVK_IC_SCHED : 1) * (NP == 3 ? 1 : MVK_IC_SCHED2), 0);
+              __builtin_amdgcn_sched_group_barrier(0x496, ic_sched(HS) * (NP == 3 ? 1 : IC_SCHED2), 0);
             }
           }
 #ifdef MVK_ICPROF
@@ -648,11 +635,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int m = 0; m < 6; ++m) {
           acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[0][PA[m]], Bw[q0][c0][PB[m]], acc0, 0, 0, 0);
-#ifdef MVK_IC_ONECHAIN
-          acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][PA[m]], Bw[q1][c1][PB[m]], acc0, 0, 0, 0);
-#else
           acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[1][PA[m]], Bw[q1][c1][PB[m]], acc1, 0, 0, 0);
-#endif
         }
         if (pr < 7) {
 #pragma unroll
@@ -665,21 +648,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // the VALU / LDS / memory work in bursts of 7-20 between the clusters).  Ask the scheduler for the pipeline
         // "1 MFMA, N others" instead (N = 4 ... 10 measured: 5-6 is best; cycles per wave at n = 5120:
         // down 8x8 254 k -> 214 k, down 4x4 262 k -> 222 k, up 4x4 218 k -> 197 k, up 8x8 174 k -> 168 k).
-        if (MVK_IC_SCHED > 0) {
 #pragma unroll
-          for (int m = 0; m < 12; ++m) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x496, MVK_IC_SCHED > 0 ? MVK_IC_SCHED : 1, 0);  // VALU | SALU | VMEM | DS | TRANS
-          }
+        for (int m = 0; m < 12; ++m) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x496, ic_sched(HS), 0);  // VALU | SALU | VMEM | DS | TRANS
         }
       }
 #ifdef MVK_ICPROF
       ic_k += IC_CLK() - ic_k0;
       const unsigned long long ic_p0 = IC_CLK();
 #endif
-#ifndef MVK_IC_ONECHAIN
       acc0 += acc1;
-#endif
       // next tile: same unit and buffer, or the first tile of the next unit in the other buffer (complete after the
       // barrier below; the last unit of the workgroup re-reads a converted copy of itself, unused)
       const char* const next_buf = (tt + 1 < T::TPU) ? abuf : nbuf;
@@ -870,13 +849,9 @@ struct WCfg {
   static constexpr int KS = SU * PIX / 16;                       // 16-pixel k-steps per unit
   static constexpr int UROWS_IMG = SPLIT_KH ? HS * AW : 4 * PIX; // staged input rows per image (one row per (i, x))
   static constexpr int UROWS = SU * UROWS_IMG, VROWS = SU * PIX;
-#ifndef MVK_IW_PAD_A
-#define MVK_IW_PAD_A 32  // tools/imgwgrad_pad.sh: 16 -> 112.8 us, 32 ... 72 -> 102-107 us (64 <-> 128 channels, n = 5120)
-#endif
-#ifndef MVK_IW_PAD_B
-#define MVK_IW_PAD_B 0
-#endif
-  static constexpr int PAD = SPLIT_KH ? MVK_IW_PAD_A : MVK_IW_PAD_B;  // row padding (bytes) of the LDS images
+  // row padding (bytes) of the LDS images; measured for the SPLIT_KH form: 16 -> 112.8 us, 32 ... 72 -> 102-107 us (64 <-> 128
+  // channels, n = 5120)
+  static constexpr int PAD = SPLIT_KH ? 32 : 0;
   static constexpr int SUB = CU * 2 + PAD, SVB = CV * 2 + PAD;   // bytes per LDS row
   static constexpr int PLANE_U = (UROWS + 1) * SUB, PLANE_V = VROWS * SVB;
   static constexpr int OFF_V = NP * PLANE_U;
@@ -937,13 +912,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int wgtype = blockIdx.x % T::WG_TYPES;
   int worker = blockIdx.x / T::WG_TYPES;
   const int workers = gridDim.x / T::WG_TYPES;
-#ifndef MVK_NO_XCDMAP
   if (T::WG_TYPES > 1 && gridDim.x % (8 * T::WG_TYPES) == 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     wgtype = slot % T::WG_TYPES;
     worker = xcd * (gridDim.x / (8 * T::WG_TYPES)) + slot / T::WG_TYPES;
   }
-#endif
   const int kh = T::SPLIT_KH ? wgtype : wave;
 
   // zero rows of the U planes of both buffers
@@ -1001,11 +974,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const long long units = g.n / T::SU;
   // readfirstlane: the 64-bit division is emitted on the vector ALU, which makes the trip count of the unit loop 'divergent'
   // for hipcc (exec-masked loop, every live-out accumulator read back per iteration: 32 v_accvgpr_read + a drain of the matrix pipe per tile)
-  const long long u0 = MVK_RFL((int)(units * worker / workers));
-  const long long u1 = MVK_RFL((int)(units * (worker + 1) / workers));
+  const long long u0 = __builtin_amdgcn_readfirstlane((int)(units * worker / workers));
+  const long long u1 = __builtin_amdgcn_readfirstlane((int)(units * (worker + 1) / workers));
   f32x4 raw[T::NF];
   auto load_f4 = [&](long long u, int k) {
-    const long long uc = (MVK_IC_ABL & 1) ? u0 : (u < u1 ? u : u1 - 1);
+    const long long uc = u < u1 ? u : u1 - 1;
     const f32x4* base = k < T::NFU ? reinterpret_cast<const f32x4*>(g.U) + uc * U_UNIT
                                    : reinterpret_cast<const f32x4*>(g.V) + uc * V_UNIT;
     raw[k] = base[ssrc[k]];
@@ -1102,14 +1075,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int b = 0; b < T::NT; ++b)
               acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Af[a][PA[m]], Bf[b][PB[m]], acc[a][b], 0, 0, 0);
       }
-#ifndef MVK_IW_SCHED
-#define MVK_IW_SCHED 4
-#endif
-      if (MVK_IW_SCHED > 0) {  // "1 MFMA, N others" instead of hipcc's MFMA clusters (see imgconv_kernel)
+      {  // "1 MFMA, N others" instead of hipcc's MFMA clusters (see imgconv_kernel)
+        constexpr int IW_SCHED = 4;
 #pragma unroll
         for (int m = 0; m < 2 * NP * T::MT * T::NT; ++m) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x496, (MVK_IW_SCHED > 0 ? MVK_IW_SCHED : 1) * (NP == 3 ? 1 : 2), 0);
+          __builtin_amdgcn_sched_group_barrier(0x496, IW_SCHED * (NP == 3 ? 1 : 2), 0);
         }
       }
       if (s + 1 < T::KS) {

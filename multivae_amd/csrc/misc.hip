@@ -67,16 +67,13 @@ __global__ __launch_bounds__(256) void pack_multi_kernel(const PackJobs jobs) {
     return;
   }
   const int total = d.Cv * d.Cu * 16;
-#ifndef MVK_PACK_TILED
-#define MVK_PACK_TILED 1
-#endif
   // Tiled form (round 4): the element-per-thread loop below reads coalesced and issues up to EIGHT scattered 2- / 4-byte stores per
   // element (two fp32 packs + 2 x 3 bf16 fragment pieces: 3.2 M partial-line writes per launch, ~20 us at the head of every
   // step).  Here a workgroup takes a tile of 8 cv x 8 cu x 16 taps through LDS and writes every destination in 16-byte pieces:
   // 8 consecutive cv of a (tap, cu) are contiguous in Wdown and form one fragment chunk of Fup, 8 consecutive cu of a (tap, cv)
   // are contiguous in Wup and form one chunk of Fdown — 1280 stores of 16 bytes per 1024 elements instead of 8192 small ones.
   // Same values in the same places.
-  if (MVK_PACK_TILED && d.kind == 0 && d.Cu % 8 == 0 && d.Cv % 8 == 0 && d.ld_down % 4 == 0 && d.col_off % 4 == 0 &&
+  if (d.kind == 0 && d.Cu % 8 == 0 && d.Cv % 8 == 0 && d.ld_down % 4 == 0 && d.col_off % 4 == 0 &&
       mvk_dev_aligned16(d.Wref) && (!d.Wdown || mvk_dev_aligned16(d.Wdown)) && (!d.Wup || mvk_dev_aligned16(d.Wup))) {
     __shared__ __attribute__((aligned(16))) float T[8][8][16];  // [cv][cu][tap]
     const int tcu = d.Cu / 8, ntiles = (d.Cv / 8) * tcu, t = threadIdx.x;

@@ -199,13 +199,11 @@ struct HeadsBwdArgs {
   long long w_sk, w_sn;  // W_h(n, k) = W_h[n * w_sn + k * w_sk]
 };
 
-#ifndef MVK_CHAIN_PRIO
-#define MVK_CHAIN_PRIO 3  // wave priority of the latency-critical chain kernels (s_setprio; 0 = default)
-#endif
+constexpr int CHAIN_PRIO = 3;  // wave priority of the latency-critical chain kernels (s_setprio; 0 = default)
 __global__ __launch_bounds__(256) void heads_bwd_kernel(const HeadsBwdArgs g) {
   // This launch heads the step's last dependent chain and runs beside the decoder's weight gradients (one 512-register MFMA wave
   // per SIMD, all 256 CUs): 17 us alone, 60-90 us there.  A higher wave priority wins the SIMD's issue arbitration against that wave.
-  if (MVK_CHAIN_PRIO) __builtin_amdgcn_s_setprio(MVK_CHAIN_PRIO);
+  __builtin_amdgcn_s_setprio(CHAIN_PRIO);
   // LDS sized by the heads' width (dynamic): 48 KB for the 2 x 20 latents of the MnistSvhn encoders instead of a fixed 62 KB — the
   // launch runs beside the decoder's weight gradients (95 / 112 KB of a CU's 160 KB): at 62 KB no workgroup of it fits beside the
   // larger one
@@ -475,13 +473,6 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(const SmallKArgs g) {
   const int n = (cg < CT ? cg : 0) * 4;
   const int m0 = blockIdx.x * R;
   f32x4 w[KP];  // w[k] = W(k, n .. n+3)
-#ifndef MVK_SK_ABL
-#define MVK_SK_ABL 0  // subtraction builds (tools/smallk_probe.py): 1 no weight loads, 2 no stores, 4 no FMA loop
-#endif
-  if (MVK_SK_ABL & 1) {
-#pragma unroll
-    for (int k = 0; k < KP; ++k) w[k] = f32x4{0.01f * k, 0.02f, 0.03f, 0.04f * threadIdx.x};
-  } else
   if (g.w_sn == 1 && (g.w_sk & 3) == 0 && mvk_dev_aligned16(g.W)) {  // [K][N] rows: one 16-byte load per k
 #pragma unroll
     for (int k = 0; k < KP; ++k)
@@ -512,12 +503,10 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(const SmallKArgs g) {
   }
   __syncthreads();
   float amax_l = 0.f;
-#ifndef MVK_SK_UNROLL
-#define MVK_SK_UNROLL 1  // rows in flight per thread (a row is ONE dependent chain of K packed FMAs): 4 measured, no difference in the step
-// (0.9735 / 0.9757 / 0.9742 / 0.9795 against 0.9761 / 0.9736 / 0.9772 / 0.9783 ms, tools/lab/r06/gpu_r06_j.sh): the round-5 loop stays
-#endif
+  // one row in flight per thread (a row is ONE dependent chain of K packed FMAs): 4 measured, no difference in the step
+  // (0.9735 / 0.9757 / 0.9742 / 0.9795 against 0.9761 / 0.9736 / 0.9772 / 0.9783 ms, tools/lab/r06/gpu_r06_j.sh): the round-5 loop stays
   if (active)
-#pragma unroll MVK_SK_UNROLL
+#pragma unroll 1
   for (int r = rg; r < R; r += rgn) {
     if (m0 + r >= g.M) continue;
     // packed fp32 FMAs (v_pk_fma_f32: two columns per instruction, the row's x broadcast to both halves): the same FMA chain per
@@ -525,7 +514,7 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(const SmallKArgs g) {
     typedef float f32x2_ __attribute__((ext_vector_type(2)));
     f32x2_ a01 = {b4[0], b4[1]}, a23 = {b4[2], b4[3]};
 #pragma unroll
-    for (int q = 0; q < ((MVK_SK_ABL & 4) ? 1 : K4); ++q) {
+    for (int q = 0; q < K4; ++q) {
       const f32x4 x = *reinterpret_cast<const f32x4*>(&xs[r][4 * q]);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -548,7 +537,7 @@ __global__ __launch_bounds__(256) void smallk_fwd_kernel(const SmallKArgs g) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] += old[j];
     }
-    if (!(MVK_SK_ABL & 2) || acc[0] == 123.456f) *dst = acc;
+    *dst = acc;
     amax_l = fmaxf(fmaxf(amax_l, fmaxf(fabsf(acc[0]), fabsf(acc[1]))), fmaxf(fabsf(acc[2]), fabsf(acc[3])));
   }
   if (g.y_amax) mvk::amax_publish(amax_l, g.y_amax, &xs[0][0]);  // uniform; xs is dead (amax_publish synchronises first)

@@ -14,18 +14,10 @@
 #include "bf3.hpp"
 #include "common.hpp"
 
-#ifndef MVK_SMALL_FWD_THREADS
 // Threads per workgroup (LDS allows 2 workgroups per CU either way).  Measured inside the MoPoE step (B=512, 3x32 ch):
 // forward 89 us at 256 threads -> 67 us at 512 -> 62 us at 1024 (more loads in flight, 56 VGPRs); backward 152 us at 256 -> 188 us at 512 (the
 // per-wave weight-gradient accumulators are replicated over twice the waves), so the two kernels differ.
-#define MVK_SMALL_FWD_THREADS 1024
-#endif
-#ifndef MVK_SMALL_DOWN_THREADS
-#define MVK_SMALL_DOWN_THREADS 512
-#endif
-#ifndef MVK_SMALL_BWD_THREADS
-#define MVK_SMALL_BWD_THREADS 256
-#endif
+constexpr int SMALL_FWD_THREADS = 1024, SMALL_DOWN_THREADS = 512, SMALL_BWD_THREADS = 256;
 
 #ifdef MVK_SUPROF
 __device__ unsigned long long* g_su_dbg = nullptr;
@@ -34,9 +26,6 @@ extern "C" int mvk_smallup_debug_buffer(unsigned long long* p) {
 }
 #endif
 
-#ifndef MVK_SUF_ABL
-#define MVK_SUF_ABL 0  // subtraction builds of small_up_fwd_bf_kernel: 1 no piece split, 2 one MFMA per tile instead of six, 4 a quarter of the column-matrix writes, 8 one tap read instead of four, 16 no activation
-#endif
 namespace {
 
 using mvk::f32x4;
@@ -262,13 +251,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
       const int idx = tid + u * NT;
       const int pos = idx >> 3, q = idx & 7;
       unsigned a0, a1, a2, b0, b1, b2;
-      if (MVK_SUF_ABL & 1) {
-        a0 = a1 = __float_as_uint(pre[u][0]), a2 = __float_as_uint(pre[u][1]);
-        b0 = b1 = __float_as_uint(pre[u][2]), b2 = __float_as_uint(pre[u][3]);
-      } else {
-        mvk::bf3_split(pre[u][0], pre[u][1], a0, a1, a2);
-        mvk::bf3_split(pre[u][2], pre[u][3], b0, b1, b2);
-      }
+      mvk::bf3_split(pre[u][0], pre[u][1], a0, a1, a2);
+      mvk::bf3_split(pre[u][2], pre[u][3], b0, b1, b2);
       const int off = pos * 64 + (((q >> 1) ^ ((pos >> 1) & 3)) << 4) + (q & 1) * 8;
       *reinterpret_cast<u32x2*>(Vb + off) = u32x2{a0, b0};
       *reinterpret_cast<u32x2*>(Vb + PLANE + off) = u32x2{a1, b1};
@@ -300,7 +284,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
         for (int a = 0; a < MT; ++a) {
           f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int t = 0; t < ((MVK_SUF_ABL & 2) ? 1 : 6); ++t) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a][PA[t]], bfr[PB[t]], c, 0, 0, 0);
+          for (int t = 0; t < 6; ++t) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[a][PA[t]], bfr[PB[t]], c, 0, 0, 0);
           acc[a][b] = c;
         }
       }
@@ -311,7 +295,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
 #pragma unroll
       for (int b = 0; b < CU; ++b)
 #pragma unroll
-        for (int r = 0; r < ((MVK_SUF_ABL & 4) ? 1 : 4); ++r) buf[(wave * WP + a * 16 + lq * 4 + r) * CS + b * 16 + l15] = acc[a][b][r];
+        for (int r = 0; r < 4; ++r) buf[(wave * WP + a * 16 + lq * 4 + r) * CS + b * 16 + l15] = acc[a][b][r];
     __syncthreads();
     float* out = U + img * per_img;
     if (NLL) {
@@ -329,8 +313,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
     } else {
 #pragma unroll
       for (int t = 0; t < NO; ++t) {
-        const float sum = (MVK_SUF_ABL & 8) ? buf[tap[t][0]] + bia[t] : ((buf[tap[t][0]] + buf[tap[t][1]]) + (buf[tap[t][2]] + buf[tap[t][3]])) + bia[t];
-        out[tid + t * NT] = (MVK_SUF_ABL & 16) ? sum : mvk_act(sum, act);
+        const float sum = ((buf[tap[t][0]] + buf[tap[t][1]]) + (buf[tap[t][2]] + buf[tap[t][3]])) + bia[t];
+        out[tid + t * NT] = mvk_act(sum, act);
       }
     }
     __syncthreads();  // the column matrix is overwritten by the next image's pieces
@@ -356,45 +340,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
 //     ds_write_b32;
 //   * the fast sigmoid in both forms.
 // Same sums otherwise (tap order, bias, NLL tail, wave-ordered row sum).
-// Round 5 experiment switches of the kernel below (compile-time; tools/suh_variants.sh builds and times them; medians of the fused
-// tail alone over three interleaved rounds on one box, base 58.2 us: XFIRST 56.2, PAIR 55.6, WREG 54.0 (shipped), NT 57.5,
-// XFIRST + WREG 65.1 (!), XFIRST + WREG + PAIR 57.3, all four 61.1 — the combinations are worse than their parts: the kernel is
-// bound by how its four barrier phases of two resident workgroups interleave, not by any one instruction stream):
-//   MVK_SUH_XFIRST  the targets' loads are issued BEFORE the next image's prefetch: vmcnt counts in order, so waiting for a
-//                   load issued behind the prefetch is waiting for the prefetch as well
-//   MVK_SUH_PAIR    a thread owns PAIRS of horizontally adjacent pixels (8-byte target loads and gradient stores, one tap table
-//                   of 8 entries instead of 24: the channel is the unrolled index)
-//   MVK_SUH_WREG    the weight fragments stay in registers for the whole launch (24 VGPRs) instead of 6 ds_read_b128 per image
-//   MVK_SUH_NT      nontemporal loads of the input map (read once) and stores of the gradient (read ~300 us later)
-#ifndef MVK_SUH_XFIRST
-#define MVK_SUH_XFIRST 0
-#endif
-#ifndef MVK_SUH_PAIR
-#define MVK_SUH_PAIR 0
-#endif
-#ifndef MVK_SUH_WREG
-#define MVK_SUH_WREG 1  // measured (tools/suh_run.sh, n = 5120, three interleaved rounds): fused tail 58.2 -> 54.0 us, plain 48.8 -> 45.7
-#endif
-#ifndef MVK_SUH_NT
-#define MVK_SUH_NT 0
-#endif
+// The weight fragments stay in registers for the whole launch (24 VGPRs) instead of 6 ds_read_b128 per image: measured (n = 5120,
+// three interleaved rounds) fused tail 58.2 -> 54.0 us, plain 48.8 -> 45.7.  The round's other forms (targets loaded before the
+// prefetch, pixel pairs per thread, nontemporal accesses) lost alone or in combination: DESIGN.md §9.
 template <int CU, int NT, bool NLL = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT / 128))) void small_up_fwd_h_kernel(
     const float* __restrict__ V, const float* __restrict__ Wref, const float* __restrict__ bias, float* __restrict__ U, int n, int act,
     mvk_prof_slot* prof, const float* __restrict__ v_amax, const float* __restrict__ X = nullptr, int xrows = 1, float inv_s2 = 1.f,
     float lconst = 0.f, float* __restrict__ rows = nullptr, float g_inv_s2 = 1.f, float* __restrict__ du_amax = nullptr) {
   mvk_prof_begin(prof);
-#ifndef MVK_SUH_GMAX
-// how the fused tail bounds max |stored gradient|: 0 = not at all (A/B), 1 = exact, per thread, 2 = exact, per wave and image,
-// 3 = from the largest row sum (wave 0 has it anyway): |g| <= |g_inv_s2| max act' sqrt(2 max_i tot_i / inv_s2), up to
-// sqrt(3072) = 55 times the true maximum (6 bits of fp16 range, no precision), no instruction outside wave 0
-#define MVK_SUH_GMAX 3
-#endif
-  float gmax = 0.f;       // ... of this thread (published at the end when du_amax is given)
-  unsigned gmax_u = 0u;   // ... of this wave, as bits (wave-uniform: a scalar register)
+  // The fused tail bounds max |stored gradient| from the largest row sum (wave 0 has it anyway): |g| <= |g_inv_s2| max act'
+  // sqrt(2 max_i tot_i / inv_s2), up to sqrt(3072) = 55 times the true maximum (6 bits of fp16 range, no precision), no
+  // instruction outside wave 0.
+  unsigned gmax_u = 0u;   // the largest row sum of this wave, as bits (wave-uniform: a scalar register)
   using mvk::f16x8;
   using mvk::u32x2;
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int CV = 32, NC = 16 * CU, CS = NC + 4, P = 256, h = 16, w = 16;
   constexpr int WP = P / (NT / 64), MT = WP / 16;
   constexpr int PLANE = P * 64, WPLANE = NC * 64;  // bytes per piece plane
@@ -434,24 +394,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
   auto prefetch = [&](long long img) __attribute__((always_inline)) {
     const f32x4* src = reinterpret_cast<const f32x4*>(V + img * P * CV);
 #pragma unroll
-    for (int u = 0; u < NV; ++u) pre[u] = MVK_SUH_NT ? __builtin_nontemporal_load(src + tid + u * NT) : src[tid + u * NT];
+    for (int u = 0; u < NV; ++u) pre[u] = src[tid + u * NT];
   };
   constexpr int H2 = 2 * h, W2 = 2 * w, per_img = CU * H2 * W2;
   constexpr int NO = per_img / NT;
-  // output -> (tap addresses in the column matrix, bias).  Plain mapping: output o = tid + t NT of the NCHW image.  PAIR mapping
-  // (NT = 512): thread = (output row tid >> 4, pixel pair tid & 15), the unrolled index is the channel: o = cu 1024 + 2 tid + e.
-  constexpr bool PAIR = MVK_SUH_PAIR && NT == 512 && H2 * W2 == 2 * NT;
-  constexpr int NTAP = PAIR ? 2 : NO;
-  int tap[NTAP][4];
+  // output -> (tap addresses in the column matrix, bias): output o = tid + t NT of the NCHW image
+  int tap[NO][4];
   float bia[NO];
 #pragma unroll
   for (int t = 0; t < NO; ++t) {
-    const int cu = PAIR ? t / 2 : (tid + t * NT) / (H2 * W2);
+    const int cu = (tid + t * NT) / (H2 * W2);
     bia[t] = bias ? bias[cu] : 0.f;
   }
 #pragma unroll
-  for (int t = 0; t < NTAP; ++t) {
-    const int o = PAIR ? 2 * tid + t : tid + t * NT;
+  for (int t = 0; t < NO; ++t) {
+    const int o = tid + t * NT;
     const int cu = o / (H2 * W2);
     const int rem = o - cu * (H2 * W2);
     const int oh = rem / W2, ow = rem - oh * W2;
@@ -466,7 +423,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
         tap[t][a * 2 + b] = ok ? (ih * w + iw) * CS + cu * 16 + kh * 4 + kw : zidx;
       }
   }
-  if (tid < 3) buf[zidx + 16 * tid] = 0.f;
+  if (tid < 3) buf[zidx + 16 * tid] = 0.f;  // the zero word the border taps read (only the first of the three is read)
   // fragment addresses (bytes inside a plane): positions = B operand, weights = A operand (both [row][32 k], k-octet lq)
   int poff[MT], woff[CU];
 #pragma unroll
@@ -479,14 +436,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
     const int c = b * 16 + l15;
     woff[b] = c * 64 + ((lq ^ ((c >> 1) & 3)) << 4);
   }
-#if MVK_SUH_WREG
   __syncthreads();  // the weight planes are complete
   f16x8 wreg[CU][2];
 #pragma unroll
   for (int b = 0; b < CU; ++b)
 #pragma unroll
     for (int p = 0; p < 2; ++p) wreg[b][p] = *reinterpret_cast<const f16x8*>(Wb + p * WPLANE + woff[b]);
-#endif
   long long img = blockIdx.x;
   if (img < n) prefetch(img);
   for (; img < n; img += gridDim.x) {
@@ -502,22 +457,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
       *reinterpret_cast<u32x2*>(Vb + PLANE + off) = u32x2{a1, b1};
     }
     __syncthreads();
-    if (!MVK_SUH_XFIRST && img + gridDim.x < n) prefetch(img + gridDim.x);
+    if (img + gridDim.x < n) prefetch(img + gridDim.x);
     float xv[NO];  // fused tail: this thread's target pixels, loaded here and first touched behind the GEMM
     if (NLL) {
       const float* xt = X + (img % xrows) * per_img;
-      if (PAIR) {
 #pragma unroll
-        for (int c = 0; c < NO / 2; ++c) {
-          const f32x2 v2 = reinterpret_cast<const f32x2*>(xt + c * H2 * W2)[tid];
-          xv[2 * c] = v2[0], xv[2 * c + 1] = v2[1];
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < NO; ++t) xv[t] = (MVK_SUF_ABL & 32) ? 0.25f : xt[tid + t * NT];
-      }
+      for (int t = 0; t < NO; ++t) xv[t] = xt[tid + t * NT];
     }
-    if (MVK_SUH_XFIRST && img + gridDim.x < n) prefetch(img + gridDim.x);
     f32x4 res[MT][CU];  // D[nn = b * 16 + 4 lq + r][pos = wave * WP + a * 16 + l15]
     {
       f16x8 pf[MT][2];
@@ -527,15 +473,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
         for (int p = 0; p < 2; ++p) pf[a][p] = *reinterpret_cast<const f16x8*>(Vb + p * PLANE + poff[a]);
 #pragma unroll
       for (int b = 0; b < CU; ++b) {
-        f16x8 wf[2];
+        f16x8 wf[2];  // (a copy on purpose: the MFMAs reading wreg[b] directly changes hipcc's register allocation)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-#if MVK_SUH_WREG
-          wf[p] = wreg[b][p];
-#else
-          wf[p] = *reinterpret_cast<const f16x8*>(Wb + p * WPLANE + woff[b]);
-#endif
-        }
+        for (int p = 0; p < 2; ++p) wf[p] = wreg[b][p];
 #pragma unroll
         for (int a = 0; a < MT; ++a) {
           f32x4 cm = f32x4{0.f, 0.f, 0.f, 0.f}, cx = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -557,9 +497,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
     float* out = U + img * per_img;
     // output t of this thread: its four taps (fixed order), bias, activation
     auto pixel = [&](int t) __attribute__((always_inline)) {
-      const int tt = PAIR ? (t & 1) : t, co = PAIR ? (t >> 1) * 16 : 0;  // PAIR: the channel is a column offset of the same taps
-      // (the zero word has a copy at zidx + 16 and zidx + 32: a border tap plus a channel offset still reads a zero)
-      const float sum = ((buf[tap[tt][0] + co] + buf[tap[tt][1] + co]) + (buf[tap[tt][2] + co] + buf[tap[tt][3] + co])) + bia[t];
+      const float sum = ((buf[tap[t][0]] + buf[tap[t][1]]) + (buf[tap[t][2]] + buf[tap[t][3]])) + bia[t];
       return act == MVK_ACT_SIGMOID ? mvk_fast_sigmoid(sum) : mvk_act(sum, act);
     };
     if (NLL) {
@@ -568,46 +506,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
 #pragma unroll
       for (int t = 0; t < NO; ++t) {
         const float r = pixel(t), dlt = r - xv[t];
-        if (!(MVK_SUF_ABL & 64)) part = fmaf(0.5f * inv_s2 * dlt, dlt, part);
+        part = fmaf(0.5f * inv_s2 * dlt, dlt, part);
         gv[t] = dlt * g_inv_s2 * mvk_act_grad_from_out(r, act);
       }
-      if (MVK_SUH_GMAX == 1) {
 #pragma unroll
-        for (int t = 0; t < NO; ++t) gmax = fmaxf(gmax, fabsf(gv[t]));
-      } else if (MVK_SUH_GMAX == 2) {
-        float gm = fabsf(gv[0]);
-#pragma unroll
-        for (int t = 1; t < NO; ++t) gm = fmaxf(gm, fabsf(gv[t]));
-        const unsigned gu = wave_max_dpp_bits(gm);
-        gmax_u = gu > gmax_u ? gu : gmax_u;
-      }
-      if (PAIR) {
-#pragma unroll
-        for (int c = 0; c < NO / 2; ++c) {
-          f32x2* dst = reinterpret_cast<f32x2*>(out + c * H2 * W2) + tid;
-          if (MVK_SUH_NT) __builtin_nontemporal_store(f32x2{gv[2 * c], gv[2 * c + 1]}, dst);
-          else *dst = f32x2{gv[2 * c], gv[2 * c + 1]};
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < NO; ++t) {
-          if (MVK_SUH_NT) __builtin_nontemporal_store(gv[t], out + tid + t * NT);
-          else out[tid + t * NT] = gv[t];
-        }
-      }
-      if (!(MVK_SUF_ABL & 64)) {
-        part = wave_sum_dpp(part);
-        if (lane == 0) buf[zidx + 1 + wave] = part;
-      }
-    } else if (PAIR) {
-#pragma unroll
-      for (int c = 0; c < NO / 2; ++c) reinterpret_cast<f32x2*>(out + c * H2 * W2)[tid] = f32x2{pixel(2 * c), pixel(2 * c + 1)};
+      for (int t = 0; t < NO; ++t) out[tid + t * NT] = gv[t];
+      part = wave_sum_dpp(part);
+      if (lane == 0) buf[zidx + 1 + wave] = part;
     } else {
 #pragma unroll
       for (int t = 0; t < NO; ++t) out[tid + t * NT] = pixel(t);
     }
     __syncthreads();  // the column matrix is overwritten by the next image's pieces
-    if (NLL && wave == 0 && !(MVK_SUF_ABL & 64)) {  // the wave partials are rewritten three barriers from now at the earliest
+    if (NLL && wave == 0) {  // the wave partials are rewritten three barriers from now at the earliest
       // (one LDS latency + a fixed shuffle tree over the NT / 64 partials: a serial loop of dependent LDS reads in thread 0 held
       // its wave back ~3 us per launch at the next barrier)
       unsigned ones = ~0u;
@@ -617,21 +528,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT / 128, NT
 #pragma unroll
       for (int off = NT / 128; off > 0; off >>= 1) tot += __shfl_xor(tot, off, 64);
       if (lane == 0) rows[img] = tot + lconst;
-      if (MVK_SUH_GMAX == 3) {
-        const unsigned tb = (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(tot));  // a sum of squares: >= 0
-        gmax_u = tb > gmax_u ? tb : gmax_u;
-      }
+      const unsigned tb = (unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(tot));  // a sum of squares: >= 0
+      gmax_u = tb > gmax_u ? tb : gmax_u;
     }
   }
-  if (MVK_SUH_GMAX == 3) {
-    if (NLL && du_amax && tid == 0) {  // one atomic per workgroup, only when it raises the published value (bf3.hpp)
-      const float cmax = act == MVK_ACT_SIGMOID ? 0.25f : 1.f;
-      const float bound = 1.001f * fabsf(g_inv_s2) * cmax * sqrtf(2.f * __uint_as_float(gmax_u) / inv_s2);
-      unsigned* const d = reinterpret_cast<unsigned*>(du_amax);
-      const unsigned mu = __float_as_uint(bound);
-      if (mu > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, mu);
-    }
-  } else if (NLL && du_amax) mvk::amax_publish_wave(MVK_SUH_GMAX == 2 ? __uint_as_float(gmax_u) : __uint_as_float(wave_max_dpp_bits(gmax)), du_amax, buf + zidx + 1);  // uniform branch; the wave-partial words are free here
+  if (NLL && du_amax && tid == 0) {  // one atomic per workgroup, only when it raises the published value (bf3.hpp)
+    const float cmax = act == MVK_ACT_SIGMOID ? 0.25f : 1.f;
+    const float bound = 1.001f * fabsf(g_inv_s2) * cmax * sqrtf(2.f * __uint_as_float(gmax_u) / inv_s2);
+    unsigned* const d = reinterpret_cast<unsigned*>(du_amax);
+    const unsigned mu = __float_as_uint(bound);
+    if (mu > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, mu);
+  }
   mvk_prof_end(prof);
 }
 
@@ -657,15 +564,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
   mvk_prof_begin(prof);
   using C = SmallCfg<CU, CV>;
   const int u_act = UACT >= 0 ? UACT : u_act_rt, v_act = VACT >= 0 ? VACT : v_act_rt;
-#ifdef MVK_ABLATE  // tools/smallup_ablate.sh: which part of the kernel bounds it (wrong results by construction)
-  const int abl = (units >> 8) & 0xff;
-  const int dephase = units >> 16;  // experiment: the second half of the grid starts `dephase` x ~0.4 us late
-  units &= 0xff;
-  if (blockIdx.x >= gridDim.x / 2)
-    for (int q = 0; q < dephase; ++q) __builtin_amdgcn_s_sleep(100);
-#else
-  constexpr int abl = 0;
-#endif
   constexpr int NW = NT / 64;    // waves per workgroup
   constexpr int WP = PU / NW;    // positions per wave
   constexpr int MT = WP / 16;    // 16-row MFMA tiles per wave
@@ -769,21 +667,19 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
     // --- stage dUpre with halo (sigmoid' applied here), bias-gradient partials, and the V tile
     const int r2s = 2 * (int)(unit & (units - 1)) * hu;  // first output row of the unit being staged
     if (DENSE) {
-      if (!(abl & 16)) {
 #pragma unroll
-        for (int k = 0; k < CU; ++k)
+      for (int k = 0; k < CU; ++k)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float v = qdu[k][e] * mvk_act_grad_from_out(quo[k][e], u_act);
-            Ds[k * 34 * 34 + dbase + e] = v;
-            dblq[k] += v;
-          }
-      }
+        for (int e = 0; e < 4; ++e) {
+          const float v = qdu[k][e] * mvk_act_grad_from_out(quo[k][e], u_act);
+          Ds[k * 34 * 34 + dbase + e] = v;
+          dblq[k] += v;
+        }
     } else
 #pragma unroll
     for (int u = 0; u < ND; ++u) {
       const int idx = tid + u * NT;
-      if (idx < nd && !(abl & 16)) {
+      if (idx < nd) {
         const int oh = r2s + (tinfo[u] & 255) - 1;
         const bool in = ((tinfo[u] >> 10) & 1) && oh >= 0 && oh < H2;
         const float v = in ? pdu[u] * mvk_act_grad_from_out(puo[u], u_act) : 0.f;  // zero padding outside the image
@@ -795,7 +691,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
       const int idx = tid + u * NT;
-      if ((DENSE || idx < n4) && !(abl & 32)) {
+      if (DENSE || idx < n4) {
         const int pos = idx / (CV / 4), q = idx - pos * (CV / 4);
         *reinterpret_cast<f32x4*>(Vs + pos * C::VS + 4 * q) = pv[u];
       }
@@ -803,7 +699,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
     SU_T(1)
     __syncthreads();
     SU_T(0)
-    if (unit + gridDim.x < nunits && !(abl & 8)) prefetch(unit + gridDim.x);
+    if (unit + gridDim.x < nunits) prefetch(unit + gridDim.x);
     SU_T(2)
     if (!DENSE && !active) continue;
     // --- backward data: dV[pos][cv] = sum_{k=(cu,kh,kw)} dUpre[cu][2i-1+kh][2j-1+kw] * W[cv][k]
@@ -816,7 +712,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
 #pragma unroll
     for (int a = 0; a < MT; ++a) po[a] = posoff[wave * WP + a * 16 + l15];
 #pragma unroll 2
-    for (int ks = 0; ks < ((abl & 1) ? 1 : C::NC / 4); ++ks) {
+    for (int ks = 0; ks < C::NC / 4; ++ks) {
       const int k = ks * 4 + lq;
       const int koff = (k >> 4) * DH * DW + ((k >> 2) & 3) * DW + (k & 3);
       float av[MT], bv[C::NTV];
@@ -831,7 +727,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[b], av[a], acc[a][b], 0, 0, 0);  // transposed tile
     }
     SU_T(3)
-    if (!(abl & 64)) {
+    {
       // operands swapped: this lane holds dV[pos = a*16 + l15][cv = b*16 + 4*lq .. +3] -> 16-byte mask reads and stores
       const long long img = unit >> (units - 1);
       const int r0 = (int)(unit & (units - 1)) * hu;
@@ -848,13 +744,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) 
             g[r] = acc[a][b][r] * mvk_act_grad_from_out(vin[r], v_act);
             dbv[b][r] += g[r];
           }
-          if (!(abl & 4)) *reinterpret_cast<f32x4*>(dv + pos * CV + cv) = g;
+          *reinterpret_cast<f32x4*>(dv + pos * CV + cv) = g;
         }
     }
     SU_T(4)
     // --- backward weight: dW[cv][k] += sum_pos V[pos][cv] * dUpre(gathered)[pos][k]; this wave's WP positions
 #pragma unroll 2
-    for (int ks = 0; ks < ((abl & 2) ? 1 : WP / 4); ++ks) {
+    for (int ks = 0; ks < WP / 4; ++ks) {
       const int kpos = wave * WP + ks * 4 + lq;
       const int pbase = posoff[kpos];
       float av[C::NTV], bv[CU];
@@ -1223,7 +1119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // lo hi') / 2048 in a main and a cross accumulator): 96 MFMAs per wave and image instead of 192, two piece planes instead of
 // three (51 KB of LDS).  Same data flow, same parity planes, same transposing reads.  The scales:
 //   gradient  s_d from du_amax x max |rowscale| — the fused tail publishes a bound of what it stores (amax protocol; from its
-//             largest row sum, MVK_SUH_GMAX), the largest row weight is found in the prologue (n floats, L2-resident).  ONE
+//             largest row sum), the largest row weight is found in the prologue (n floats, L2-resident).  ONE
 //             scale for the launch: the weight gradient accumulates over the images of a workgroup in registers;
 //   V         s_v from v_amax, the bound the 64 -> 32 launch published; weights: the workgroup computes max |W| itself.
 // The ReLU mask of dV comes from the pieces of V: V >= 0 by contract (v_act = ReLU), and V > 0 iff one of its two pieces is
@@ -1628,7 +1524,7 @@ static int launch_fwd(const float* V, const float* Wref, const float* bias, floa
                       hipStream_t s, const float* X = nullptr, int xrows = 1, float scale = 1.f, float* rows = nullptr,
                       float grad_weight = 1.f, const float* v_amax = nullptr, float* du_amax = nullptr) {
   const size_t lds = fwd_lds<CU, CV>(h * w);
-  constexpr int NT = MVK_SMALL_FWD_THREADS;
+  constexpr int NT = SMALL_FWD_THREADS;
   if (lds > 64 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(small_up_fwd_kernel<CU, CV, NT, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1746,7 +1642,7 @@ static int launch_bwd(const float* dU, const float* Uout, int u_act, const float
     }
   }
   const size_t lds = bwd_lds<CU, CV>(h / units, w);
-  constexpr int NT = MVK_SMALL_BWD_THREADS;
+  constexpr int NT = SMALL_BWD_THREADS;
   if (lds > 64 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(small_up_bwd_kernel<CU, CV, NT, 256, 2, -1, -1, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1763,15 +1659,9 @@ static int launch_bwd(const float* dU, const float* Uout, int u_act, const float
   mvk_prof_slot* prof = mvk::prof_next(6, 4.0 * n * h * w * (2.0 * CV + 8.0 * CU));
   static const int occ_env = mvk_tune("MVK_SMALL_BWD_OCC") ? atoi(mvk_tune("MVK_SMALL_BWD_OCC")) : 3;
   const bool spec = u_act == MVK_ACT_SIGMOID && v_act == MVK_ACT_RELU;
-#ifdef MVK_ABLATE
-  const int abl_bits = ((mvk_tune("MVK_ABLATE") ? atoi(mvk_tune("MVK_ABLATE")) : 0) << 8) |
-                       ((mvk_tune("MVK_DEPHASE") ? atoi(mvk_tune("MVK_DEPHASE")) : 0) << 16);
-#else
-  constexpr int abl_bits = 0;
-#endif
 #define MVK_SUB_LAUNCH(PU_, OCC_, UA_, VA_, UNITS_, DENSE_)                                                               \
   hipLaunchKernelGGL((small_up_bwd_kernel<CU, CV, NT, PU_, OCC_, UA_, VA_, DENSE_>), dim3(grid), dim3(NT), lds, s, dU, Uout, \
-                     u_act, V, v_act, Wref, dV, ws, n, h, w, (UNITS_) | abl_bits, prof)
+                     u_act, V, v_act, Wref, dV, ws, n, h, w, UNITS_, prof)
   static const int dense_env = mvk_tune("MVK_SMALL_BWD_DENSE") ? atoi(mvk_tune("MVK_SMALL_BWD_DENSE")) : 1;  // A/B switch
   const bool dense = dense_env && h == 16 && w == 16 && NT == 256 && mvk_aligned16(dU) && mvk_aligned16(Uout);
   if (units == 2 && occ_env == 4) {
@@ -1807,7 +1697,7 @@ template <int CU, int CV>
 static int launch_down_fwd(const float* U, const float* Wdown, const float* bias, float* V, int n, int h, int w, int act,
                            hipStream_t s, int wref) {
   using C = SmallCfg<CU, CV>;
-  constexpr int NT = MVK_SMALL_DOWN_THREADS;
+  constexpr int NT = SMALL_DOWN_THREADS;
   const int P = h * w, DH = 2 * h + 2, DW = 2 * w + 2;
   const size_t lds = ((size_t)C::NC * C::WT + ((CU * DH * DW + 3) & ~3) + P) * sizeof(float);
   const int grid = n < 1024 ? n : 1024;  // persistent: up to 4 workgroups per CU, each loops over images with prefetch

@@ -1,15 +1,11 @@
-"""Time the six large convolution GEMMs of the step under experiment flags (run on the GPU box).
-   LIB=multivae_amd/libmvk_exper.so FLAGS=<bits> python tools/bf_probe.py
-   bits: 1 no split arithmetic, 2 no global loads, 16 no split + no LDS writes, 32 no fragment reads/MFMA"""
+"""Time the six large convolution GEMMs of the step (run on the GPU box).
+   LIB=<a -DMVK_PHASES build of the library> python tools/bf_probe.py    also prints the per-phase cycle counters"""
 import ctypes as C, os, sys, torch
 sys.path.insert(0, ".")
 from multivae_amd import _lib
 lib = _lib.load(os.environ.get("LIB"))
 from multivae_amd import kernels as K
 d = torch.device("cuda:0")
-if os.environ.get("LIB"):
-    lib.mvk_debug_set_flags.argtypes = [C.c_int]
-    lib.mvk_debug_set_flags(int(os.environ.get("FLAGS", "0")))
 dbg = torch.zeros(8, dtype=torch.int64, device=d)
 if os.environ.get("LIB"):
     lib.mvk_debug_set_phase_buffer.argtypes = [C.c_void_p]
@@ -33,7 +29,6 @@ dg3 = torch.randn(n, 16, 16, 32, device=d); g2 = torch.relu(torch.randn(n, 8, 8,
 dg2 = torch.randn(n, 8, 8, 64, device=d); g1 = torch.relu(torch.randn(n, 4, 4, 128, device=d))
 w2 = torch.randn(64, 32, 4, 4, device=d) * 0.05; w1 = torch.randn(128, 64, 4, 4, device=d) * 0.05
 wd2, wu2 = K.pack_conv(w2); wd1, wu1 = K.pack_conv(w1)
-print("FLAGS", os.environ.get("FLAGS", "0"))
 probe("F1 up  128->64 4x4  (M=81920x4 N=64 K=512)", lambda: K.conv_up(g1, wu1, None, n, 4, 4, 64, 128, 1))
 probe("F2 up  64->32  8x8  (M=327680x4 N=32 K=256)", lambda: K.conv_up(g2, wu2, None, n, 8, 8, 32, 64, 1))
 probe("B1 wgrad 64,32      (M=1024 N=32 K=327680)", lambda: K.conv_wgrad(dg3, g2, w2, n, 8, 8, 32, 64))

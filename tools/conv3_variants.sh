@@ -1,6 +1,6 @@
 #!/bin/bash
-# Variant builds of conv3rs.hip (one instantiation: 64 -> 64 channels) for A/B probes on the GPU box:
-#   bash tools/conv3_variants.sh NAME "-DMVK_C3_SCHED=5 ..." [NAME2 "flags2" ...]   -> build/v/libmvk_NAME.so
+# Variant builds of conv3rs.hip (one instantiation: 64 -> 64 channels) for probes on the GPU box:
+#   bash tools/conv3_variants.sh NAME "-DMVK_C3PROF" [NAME2 "flags2" ...]   -> build/v/libmvk_NAME.so
 # build/ is git-ignored but travels with gpurun; tools/conv3_probe.py picks a library through MVK_LIB_PATH.
 set -e
 cd "$(dirname "$0")/../multivae_amd/csrc"
