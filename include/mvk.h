@@ -114,6 +114,28 @@ int mvk_gauss_sample_kl_fwd(const float* mu, const float* lv, const float* eps, 
 int mvk_gauss_sample_kl_bwd(const float* mu, const float* lv, const float* eps, const float* dw, const float* gkl,
                             int K, int B, int L, float* dmu, float* dlv, void* stream);
 
+/* Conditional latent (CVAE, cvae_model.py:145-172): the K samples of q = N(mu, exp(lv)), the conditioning data and the KL to a
+ * learned prior in ONE launch, written as the decoder's input.  mu, lv [B,L]; pmu, plv [B,L], both given or both NULL (NULL = the
+ * N(0,I) prior; the NULL form and two arrays of zeros write the same bits); eps [K,B,L]; cond: HOST array of n_cond device
+ * pointers, piece j is [B, cond_dims[j]] (cond_dims: HOST array, every entry >= 1), 0 <= n_cond <= MVK_MAX_MODALITIES,
+ * C = sum_j cond_dims[j].  Outputs: zc [K,B,L+C], every entry written once:
+ *   zc[k,b,:L] = mu[b] + exp(lv[b] / 2) eps[k,b];   zc[k,b,L+off_j : L+off_j+C_j] = cond[j][b] for every k (bit-exact copies);
+ * kl_rows [B] (nullable: generating from the prior needs the sample only) =
+ *   1/2 sum_l (plv - lv + exp(lv - plv) + (mu - pmu)^2 exp(-plv) - 1)     (base_utils.py:111-119).
+ * L + C may be odd (rows of zc are then not 16-byte aligned: the copy is scalar); the copy of the conditioning columns is spread
+ * over workgroups of its own.  No atomics, bit-reproducible, B = 0 is MVK_OK and writes nothing.
+ * bwd: dzc [K,B,L+C] (nullable; only the first L columns of each row are read, at row stride L + C: the conditioning data gets
+ * no gradient), gkl [B] (nullable) -> dmu, dlv [B,L] and dpmu, dplv [B,L] (NULL exactly when pmu is NULL), all OVERWRITTEN,
+ * everything recomputed from the inputs:
+ *   dmu = sum_k dz + gkl (mu - pmu) exp(-plv);        dlv  = 1/2 exp(lv/2) sum_k dz eps + gkl 1/2 (exp(lv - plv) - 1);
+ *   dpmu = -gkl (mu - pmu) exp(-plv);                 dplv = gkl 1/2 (1 - exp(lv - plv) - (mu - pmu)^2 exp(-plv)). */
+int mvk_cond_latent_fwd(const float* mu, const float* lv, const float* pmu, const float* plv, const float* eps,
+                        const float* const* cond, const int* cond_dims, int n_cond, int K, int B, int L, float* zc,
+                        float* kl_rows, void* stream);
+int mvk_cond_latent_bwd(const float* mu, const float* lv, const float* pmu, const float* plv, const float* eps,
+                        const float* dzc, const float* gkl, int K, int B, int L, int C, float* dmu, float* dlv,
+                        float* dpmu, float* dplv, void* stream);
+
 /* MVAE (models/mvae/mvae_model.py:56-118): for each of the S subsets of the objective (subset_bits: HOST array, bit m
  * = modality m), the product of the AVAILABLE experts of the subset and the N(0,I) prior in the log-sum-exp form of
  * `stable_poe` (base_utils.py:133-147; a missing modality has log-variance +inf, mvae_model.py:71-75), one sample

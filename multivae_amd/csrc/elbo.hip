@@ -907,6 +907,123 @@ __global__ __launch_bounds__(256) void gauss_sample_kl_bwd_kernel(const float* _
   dlv[o] = 0.5f * sd * sdwe + gk * 0.5f * (expf(v) - 1.0f);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Conditional latent (CVAE, cvae_model.py:145-172): K reparameterised samples of q = N(mu, exp(lv)) written straight into the
+// decoder input zc [K,B,L+C] beside the conditioning data, and KL(q || N(pmu, exp(plv))) per row (base_utils.py:111-119; a
+// NULL prior is N(0, I)).  One launch, two roles by block index: the first (B + 3) / 4 workgroups take one wave per row
+// (sample + KL, lanes stride over L); the others copy the conditioning columns, grid-strided over [B, C] with the K slabs
+// written from one read, so a whole image of conditioning data never queues behind a row's reduction.  VEC: 16-byte copies;
+// the host picks it only when L, every C_j and every base address keep each row of zc 16-byte aligned (odd L + C: scalar).
+// Contraction is off in both kernels: the NULL prior and a prior of zeros then give the same bits whatever the compiler
+// folds (x - 0, x * 1 and exp(-0) are exact; a fused multiply-add of a folded product would not be).
+// ---------------------------------------------------------------------------------------------------------
+struct CondTable {
+  const float* p[MAXM];
+  int dim[MAXM];
+  int off[MAXM];
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void cond_latent_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv,
+                                                              const float* __restrict__ pmu, const float* __restrict__ plv,
+                                                              const float* __restrict__ eps, const CondTable ct, int n_cond,
+                                                              int K, int B, int L, int C, int row_blocks,
+                                                              float* __restrict__ zc, float* __restrict__ kl_rows,
+                                                              mvk_prof_slot* prof) {
+#pragma clang fp contract(off)
+  mvk_prof_begin(prof);
+  const long long W = (long long)L + C;
+  if ((int)blockIdx.x < row_blocks) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b < B) {
+      float kl = 0.f;
+      for (int l = lane; l < L; l += 64) {
+        const long long o = (long long)b * L + l;
+        const float m = mu[o], v = lv[o];
+        const float pm = pmu ? pmu[o] : 0.f, pl = plv ? plv[o] : 0.f;
+        const float d = m - pm;
+        kl += 0.5f * ((pl - v) + expf(v - pl) + d * d * expf(-pl) - 1.0f);
+        const float sd = expf(0.5f * v);
+        for (int k = 0; k < K; ++k) {
+          const long long r = (long long)k * B + b;
+          zc[r * W + l] = m + sd * eps[r * L + l];
+        }
+      }
+      kl = wave_sum(kl);
+      if (lane == 0 && kl_rows) kl_rows[b] = kl;
+    }
+  } else {
+    constexpr int V = VEC ? 4 : 1;
+    const int cu = C / V;  // copy units per row
+    const long long units = (long long)B * cu;
+    const long long stride = (long long)(gridDim.x - row_blocks) * 256;
+    for (long long u = (long long)(blockIdx.x - row_blocks) * 256 + threadIdx.x; u < units; u += stride) {
+      const int b = (int)(u / cu);
+      const int c = (int)(u - (long long)b * cu) * V;
+      const float* src = ct.p[0];
+      int cj = ct.dim[0], co = 0;
+#pragma unroll
+      for (int j = 1; j < MAXM; ++j) {
+        if (j < n_cond && c >= ct.off[j]) {
+          src = ct.p[j];
+          cj = ct.dim[j];
+          co = ct.off[j];
+        }
+      }
+      const float* s = src + (long long)b * cj + (c - co);
+      float* dst = zc + (long long)b * W + L + c;
+      if constexpr (VEC) {
+        const float4 x = *reinterpret_cast<const float4*>(s);
+        for (int k = 0; k < K; ++k) *reinterpret_cast<float4*>(dst + (long long)k * B * W) = x;
+      } else {
+        const float x = *s;
+        for (int k = 0; k < K; ++k) dst[(long long)k * B * W] = x;
+      }
+    }
+  }
+  mvk_prof_end_wave(prof);
+}
+
+// One thread per (b, l); everything is recomputed from the inputs.  dzc is read at row stride L + C, first L columns only.
+__global__ __launch_bounds__(256) void cond_latent_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv,
+                                                              const float* __restrict__ pmu, const float* __restrict__ plv,
+                                                              const float* __restrict__ eps, const float* __restrict__ dzc,
+                                                              const float* __restrict__ gkl, int K, int B, int L, int C,
+                                                              float* __restrict__ dmu, float* __restrict__ dlv,
+                                                              float* __restrict__ dpmu, float* __restrict__ dplv,
+                                                              mvk_prof_slot* prof) {
+#pragma clang fp contract(off)
+  mvk_prof_begin(prof);
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o < (long long)B * L) {
+    const long long W = (long long)L + C;
+    const int b = (int)(o / L);
+    const int l = (int)(o - (long long)b * L);
+    const float m = mu[o], v = lv[o];
+    const float pm = pmu ? pmu[o] : 0.f, pl = plv ? plv[o] : 0.f;
+    float sdz = 0.f, sdze = 0.f;
+    if (dzc) {
+      for (int k = 0; k < K; ++k) {
+        const long long r = (long long)k * B + b;
+        const float g = dzc[r * W + l];
+        sdz += g;
+        sdze += g * eps[r * L + l];
+      }
+    }
+    const float gk = gkl ? gkl[b] : 0.f;
+    const float d = m - pm, ip = expf(-pl), r = expf(v - pl);
+    const float a = gk * d * ip;
+    dmu[o] = sdz + a;
+    dlv[o] = 0.5f * expf(0.5f * v) * sdze + gk * 0.5f * (r - 1.0f);
+    if (dpmu) {
+      dpmu[o] = -a;
+      dplv[o] = gk * 0.5f * (1.0f - r - d * d * ip);
+    }
+  }
+  mvk_prof_end_wave(prof);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1085,6 +1202,59 @@ int mvk_gauss_sample_kl_bwd(const float* mu, const float* lv, const float* eps, 
   hipLaunchKernelGGL(gauss_sample_kl_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, mvk_stream(stream),
                      mu, lv, eps, dw, gkl, K, B, L, dmu, dlv);
   MVK_CHECK_LAUNCH();
+  return MVK_OK;
+}
+
+int mvk_cond_latent_fwd(const float* mu, const float* lv, const float* pmu, const float* plv, const float* eps,
+                        const float* const* cond, const int* cond_dims, int n_cond, int K, int B, int L, float* zc,
+                        float* kl_rows, void* stream) {
+  if (!mu || !lv || !eps || !zc || K < 1 || L < 1 || n_cond < 0 || n_cond > MAXM) return MVK_EINVAL;
+  if ((pmu == nullptr) != (plv == nullptr) || (n_cond > 0 && (!cond || !cond_dims))) return MVK_EINVAL;
+  CondTable ct{};
+  long long Cl = 0;
+  bool vec = L % 4 == 0 && mvk_aligned16(zc);
+  for (int j = 0; j < n_cond; ++j) {
+    if (!cond[j] || cond_dims[j] < 1) return MVK_EINVAL;
+    ct.p[j] = cond[j];
+    ct.dim[j] = cond_dims[j];
+    ct.off[j] = (int)Cl;
+    Cl += cond_dims[j];
+    if (Cl + L > 0x7fffffffLL) return MVK_EINVAL;
+    vec = vec && cond_dims[j] % 4 == 0 && mvk_aligned16(cond[j]);
+  }
+  if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
+  const int C = (int)Cl;
+  const int row_blocks = (B + 3) / 4;
+  const long long units = (long long)B * (vec ? C / 4 : C);
+  const long long want = (units + 255) / 256;
+  const int copy_blocks = (int)(want < 2048 ? want : 2048);
+  const double bytes = 4.0 * B * L * ((pmu ? 4.0 : 2.0) + 2.0 * K) + 4.0 * B * C * (1.0 + K) + (kl_rows ? 4.0 * B : 0.0);
+  mvk_prof_slot* prof = mvk::prof_next(11, bytes);
+  if (vec)
+    hipLaunchKernelGGL(cond_latent_fwd_kernel<true>, dim3(row_blocks + copy_blocks), dim3(256), 0, mvk_stream(stream), mu,
+                       lv, pmu, plv, eps, ct, n_cond, K, B, L, C, row_blocks, zc, kl_rows, prof);
+  else
+    hipLaunchKernelGGL(cond_latent_fwd_kernel<false>, dim3(row_blocks + copy_blocks), dim3(256), 0, mvk_stream(stream), mu,
+                       lv, pmu, plv, eps, ct, n_cond, K, B, L, C, row_blocks, zc, kl_rows, prof);
+  MVK_CHECK_LAUNCH();
+  mvk::prof_fold(prof, mvk_stream(stream));
+  return MVK_OK;
+}
+
+int mvk_cond_latent_bwd(const float* mu, const float* lv, const float* pmu, const float* plv, const float* eps,
+                        const float* dzc, const float* gkl, int K, int B, int L, int C, float* dmu, float* dlv,
+                        float* dpmu, float* dplv, void* stream) {
+  if (!mu || !lv || !eps || !dmu || !dlv || K < 1 || L < 1 || C < 0) return MVK_EINVAL;
+  if ((pmu == nullptr) != (plv == nullptr) || (dpmu == nullptr) != (pmu == nullptr) || (dplv == nullptr) != (pmu == nullptr))
+    return MVK_EINVAL;
+  if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
+  const long long n = (long long)B * L;
+  const double bytes = 4.0 * B * L * ((pmu ? 8.0 : 4.0) + (dzc ? 2.0 * K : 0.0)) + (gkl ? 4.0 * B : 0.0);
+  mvk_prof_slot* prof = mvk::prof_next(11, bytes);
+  hipLaunchKernelGGL(cond_latent_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, mvk_stream(stream), mu, lv,
+                     pmu, plv, eps, dzc, gkl, K, B, L, C, dmu, dlv, dpmu, dplv, prof);
+  MVK_CHECK_LAUNCH();
+  mvk::prof_fold(prof, mvk_stream(stream));
   return MVK_OK;
 }
 

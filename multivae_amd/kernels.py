@@ -2082,6 +2082,50 @@ class GaussSampleKLFn(Function):
         return None, dmu, dlv
 
 
+class CondLatentFn(Function):
+    """(mu, lv) [B,L], prior (pmu, plv) [B,L] or (None, None) = N(0, I), eps [K,B,L], conditioning pieces [B, ...] ->
+    zc [K,B,L+C] (the samples beside the flattened conditioning data: the conditional decoder's input), kl_rows [B]
+    (mvk_cond_latent_fwd/bwd; CVAE).  want_kl=False: the sample only (kl_rows is None).  The pieces get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eps, mu, lv, pmu, plv, want_kl, *cond):
+        eps, mu, lv = _c(eps), _c(mu), _c(lv)
+        if (pmu is None) != (plv is None):
+            raise ValueError("CondLatentFn: the prior's mean and log-variance are given together or not at all")
+        pmu, plv = (None, None) if pmu is None else (_c(pmu), _c(plv))
+        K, B, L = eps.shape
+        pieces = [_c(t.reshape(B, -1)) for t in cond]
+        dims = (C.c_int * max(len(pieces), 1))(*[int(p.shape[1]) for p in pieces])
+        Cc = sum(int(p.shape[1]) for p in pieces)
+        zc = _new((K, B, L + Cc), eps)
+        kl = _new((B,), eps) if want_kl else None
+        call("mvk_cond_latent_fwd", ptr(mu), ptr(lv), ptr(pmu), ptr(plv), ptr(eps), ptr_array(pieces), dims, len(pieces), K, B, L,
+             ptr(zc), ptr(kl), stream_ptr())
+        ctx.save_for_backward(eps, mu, lv, *(() if pmu is None else (pmu, plv)))
+        ctx.C = Cc
+        ctx.n_cond = len(cond)
+        if kl is None:
+            return zc, None
+        return zc, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dzc, dkl):
+        dev = ctx.saved_tensors[0].device
+        schedule.wait_loss(dev)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(dev)
+        eps, mu, lv = ctx.saved_tensors[:3]
+        pmu, plv = ctx.saved_tensors[3:] if len(ctx.saved_tensors) > 3 else (None, None)
+        K, B, L = eps.shape
+        dzc = _c(dzc) if dzc is not None else None
+        dkl = _c(dkl) if dkl is not None else None
+        dmu, dlv = torch.empty_like(mu), torch.empty_like(lv)
+        dpmu, dplv = (None, None) if pmu is None else (torch.empty_like(pmu), torch.empty_like(plv))
+        call("mvk_cond_latent_bwd", ptr(mu), ptr(lv), ptr(pmu), ptr(plv), ptr(eps), ptr(dzc), ptr(dkl), K, B, L, ctx.C, ptr(dmu),
+             ptr(dlv), ptr(dpmu), ptr(dplv), stream_ptr())
+        return (None, dmu, dlv, dpmu, dplv, None) + (None,) * ctx.n_cond
+
+
 class NexusAggregateFn(Function):
     """msgs_m [B, D] -> (agg [B, D], keep [B, M]): the Nexus message mean over the kept modalities (mvk_nexus_aggregate_fwd/bwd,
     nexus_model.py:209-254).  Keep set: masks (list of M bool [B]), keep_in [B, M], or FPD from u [B, M + 1] uniforms on [0, 1)

@@ -9,7 +9,8 @@ from .mvtcae import MVTCAE, MVTCAEConfig
 from .crmvae import CRMVAE, CRMVAEConfig
 from .dmvae import DMVAE, DMVAEConfig
 from .nexus import Nexus, NexusConfig
+from .cvae import CVAE, CVAEConfig
 from .auto_model import AutoConfig, AutoModel  # noqa: E402  (needs the model classes above)
 
 __all__ = ["BaseAEConfig", "BaseMultiVAE", "BaseMultiVAEConfig", "ModelOutput", "MMVAE", "MMVAEConfig", "MoPoE",
-           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig"]
+           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig", "CVAE", "CVAEConfig"]

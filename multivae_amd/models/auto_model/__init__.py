@@ -4,12 +4,12 @@ reference load here and folders written by `BaseModel.save` load in the referenc
 import json
 import os
 
-from .. import CRMVAE, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig
+from .. import CRMVAE, CVAE, CVAEConfig, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig
 from ..base import BaseMultiVAEConfig
 
 _MODELS = {"JMVAEConfig": (JMVAE, JMVAEConfig), "MMVAEConfig": (MMVAE, MMVAEConfig), "MoPoEConfig": (MoPoE, MoPoEConfig),
            "MVTCAEConfig": (MVTCAE, MVTCAEConfig), "MVAEConfig": (MVAE, MVAEConfig), "CRMVAEConfig": (CRMVAE, CRMVAEConfig), "DMVAEConfig": (DMVAE, DMVAEConfig), "MMVAEPlusConfig": (MMVAEPlus, MMVAEPlusConfig),
-           "NexusConfig": (Nexus, NexusConfig)}
+           "NexusConfig": (Nexus, NexusConfig), "CVAEConfig": (CVAE, CVAEConfig)}
 
 
 def _name(json_path):

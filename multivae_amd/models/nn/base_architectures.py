@@ -25,6 +25,20 @@ class BaseDecoder(nn.Module):
         raise NotImplementedError()
 
 
+class BaseConditionalDecoder(BaseDecoder):
+    """Conditional decoder plugin base (`multivae/models/nn/base_architectures.py:102-143`): forward(z [n, latent_dim],
+    cond_mods: dict of conditioning tensors [n, ...]) returns a ModelOutput with `reconstruction`.  A subclass sets `latent_dim`.
+    A decoder that also defines `forward_concatenated(zc)` on the assembled input [*, latent_dim + C] (the conditioning data
+    flattened and appended in `cond_mods` order) is given that input by CVAE's training step instead."""
+
+    def __init__(self):
+        BaseDecoder.__init__(self)
+        self.latent_dim = None
+
+    def forward(self, z, cond_mods: dict):
+        raise NotImplementedError()
+
+
 class BaseJointEncoder(nn.Module):
     """Joint encoder plugin base (`multivae/models/nn/base_architectures.py`): forward(x: dict of modality tensors)
     returns a ModelOutput with `embedding` and `log_covariance`."""

@@ -15,7 +15,7 @@ from torch import nn
 from ... import kernels, schedule
 from ..base.base_config import BaseAEConfig
 from ..base.base_utils import ModelOutput
-from .base_architectures import BaseDecoder, BaseEncoder, BaseJointEncoder, BaseMultilatentEncoder
+from .base_architectures import BaseConditionalDecoder, BaseDecoder, BaseEncoder, BaseJointEncoder, BaseMultilatentEncoder
 
 
 class Encoder_VAE_MLP(BaseEncoder):
@@ -172,6 +172,25 @@ class MultipleHeadJointEncoder(BaseJointEncoder):
         params += [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
         mu, lv = kernels.MLPEncoderFn.apply(h, *params)
         return ModelOutput(embedding=mu, log_covariance=lv)
+
+
+class ConditionalDecoderMLP(BaseConditionalDecoder):
+    """`default_architectures.py:325-347`: a Decoder_AE_MLP over [z, flattened conditioning data] (state_dict keys
+    `network.layers.0.0.weight`, ...)."""
+
+    def __init__(self, latent_dim: int, cond_data_dims: dict, data_dim: tuple):
+        BaseConditionalDecoder.__init__(self)
+        self.latent_dim = latent_dim
+        self.all_dim = int(latent_dim + sum(int(np.prod(d)) for d in cond_data_dims.values()))
+        self.network = Decoder_AE_MLP(BaseAEConfig(input_dim=tuple(data_dim), latent_dim=self.all_dim))
+
+    def forward(self, z: torch.Tensor, cond_mods: dict):
+        return self.network(torch.cat([z] + [c.reshape(z.shape[0], -1) for c in cond_mods.values()], dim=1))
+
+    def forward_concatenated(self, zc: torch.Tensor):
+        """OPT-IN entry of CVAE's training step: zc [*, latent_dim + C] already holds z beside the conditioning data
+        (kernels.CondLatentFn wrote it in one launch), so nothing is concatenated here."""
+        return self.network(zc)
 
 
 def BaseDictEncoders(input_dims: dict, latent_dim: int):
