@@ -877,6 +877,49 @@ int mvk_nexus_top_nll_bwd(const float* const* z, const float* const* r, const ui
                           const float* gamma, const int* adapt, int M, int B, const float* const* grows, const float* q,
                           const float* s2, float* work, float* const* dr, void* stream);
 
+/* Gaussian-mixture sampler: full-covariance EM on the device.  Replaces samplers/gaussian_mixture/gaussian_mixture_sampler.py:90-112
+ * (sklearn.mixture.GaussianMixture(covariance_type="full").fit on the host copy of the embeddings) and :148-164 (gmm.sample);
+ * the arithmetic is scikit-learn's _estimate_log_gaussian_prob, _estimate_gaussian_parameters,
+ * _estimate_gaussian_covariances_full, _compute_precision_cholesky and the loop of BaseMixture.fit.  Per-row arithmetic is fp32,
+ * every sum over rows and the per-component finish (regularisation, Cholesky, triangular inverse, log-determinant) are fp64,
+ * outputs are fp32.  Bit-reproducible: per-workgroup partials go to `scratch` (mvk_gmm_scratch_bytes(L, C) bytes, independent of
+ * N, 8-byte aligned) and are added in workgroup order.  1 <= L <= 64, 1 <= C <= 64 (else MVK_EINVAL); N = 0 is MVK_OK and writes
+ * nothing.
+ *   X [N,L] rows; weights [C]; means [C,L]; covs [C,L,L]; cov_chol [C,L,L] = the lower Cholesky factor of covs; prec_chol [C,L,L] =
+ *   P_c = (cov_chol_c^-1)^T, upper triangular (scikit-learn's precisions_cholesky_); logdet [C] = sum ln diag P_c; resp [N,C].
+ * mvk_gmm_estep, soft (hard = 0): resp = exp(log p(x_n, c) - lse_n), log p(x_n, c) = -1/2 (L ln 2 pi + |(x_n - mu_c) P_c|^2) +
+ *   logdet[c] + ln w_c; row_out [N] (nullable) = lse_n; lb (nullable, DEVICE double) = mean_n lse_n.  Hard (hard = 1: identity
+ *   precisions, equal weights; weights, prec_chol, logdet and lb are ignored): resp = one-hot of argmin_c |x_n - mu_c|^2 (first
+ *   minimum), row_out = that minimum, labels [N] int32 (nullable) in / out, changed (nullable, device int32) = number of rows
+ *   whose label changed: k-means (Lloyd) is this and mvk_gmm_mstep with means_only, k-means++ seeding reads row_out.
+ * mvk_gmm_mstep: n_c = sum_n resp[n,c] + 10 FLT_EPSILON, means = sum resp x / n_c, covs = sum resp (x - mu_c)(x - mu_c)^T / n_c +
+ *   reg_covar I centred on the NEW means (a second pass over the rows), weights = n_c / sum_c n_c, then cov_chol, prec_chol,
+ *   logdet; a pivot that is not > 0 fills that component's cov_chol, prec_chol and logdet with NaN.  means_only: only means.
+ * mvk_gmm_em_step: one iteration of BaseMixture.fit: E, M, then on `state` (DEVICE, 8 doubles, MVK_GMM_STATE_*; the caller sets
+ *   LB = -inf and everything else 0 before the first step): PREV = LB, LB = the E-step's lower bound, ITER += 1, CONVERGED =
+ *   |LB - PREV| < tol.  STATUS becomes 1 when a Cholesky pivot is not > 0 and 2 when the lower bound is not finite.  A step
+ *   enqueued when CONVERGED or STATUS is non-zero changes nothing, so the host may enqueue several steps and read the block once.
+ * mvk_gmm_sample: z[i] = means[comp[i]] + cov_chol[comp[i]] eps[i]; comp [n] int32, eps and z [n,L] (a component index outside
+ *   [0, C) gives a NaN row). */
+#define MVK_GMM_STATE_ITER 0
+#define MVK_GMM_STATE_PREV 1
+#define MVK_GMM_STATE_LB 2
+#define MVK_GMM_STATE_CONVERGED 3
+#define MVK_GMM_STATE_STATUS 4
+#define MVK_GMM_STATE_PENDING 5 /* the lower bound of the step in flight */
+#define MVK_GMM_STATE_DOUBLES 8
+int mvk_gmm_scratch_bytes(int L, int C, int64_t* bytes);
+int mvk_gmm_estep(const float* X, int64_t N, int L, int C, const float* weights, const float* means, const float* prec_chol,
+                  const float* logdet, int hard, float* resp, float* row_out, int32_t* labels, int32_t* changed, double* lb,
+                  void* scratch, void* stream);
+int mvk_gmm_mstep(const float* X, const float* resp, int64_t N, int L, int C, double reg_covar, int means_only, float* weights,
+                  float* means, float* covs, float* cov_chol, float* prec_chol, float* logdet, void* scratch, void* stream);
+int mvk_gmm_em_step(const float* X, int64_t N, int L, int C, double reg_covar, double tol, float* weights, float* means,
+                    float* covs, float* cov_chol, float* prec_chol, float* logdet, float* resp, double* state, void* scratch,
+                    void* stream);
+int mvk_gmm_sample(const float* means, const float* cov_chol, const int32_t* comp, const float* eps, int64_t n, int L, int C,
+                   float* z, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -204,7 +204,14 @@ PROTOTYPES = {
     "mvk_nexus_aggregate_bwd": [_p, _p, _i, _i, _i, _p, _p],
     "mvk_nexus_top_nll_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
     "mvk_nexus_top_nll_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p],
+    "mvk_gmm_scratch_bytes": [_i, _i, C.POINTER(C.c_int64)],
+    "mvk_gmm_estep": [_p, _i64, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mvk_gmm_mstep": [_p, _p, _i64, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mvk_gmm_em_step": [_p, _i64, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mvk_gmm_sample": [_p, _p, _p, _p, _i64, _i, _i, _p, _p],
 }
+GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
+GMM_STATE_DOUBLES = 8
 
 _lib = None
 

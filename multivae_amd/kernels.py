@@ -2522,3 +2522,66 @@ def joint_nll(decode_rows, z, locs, sds, family=FAMILY["normal"], prior_loc=None
         lw = iwae_logw(zc, rows, [t[b0:b1] for t in locs], [t[b0:b1] for t in sds], family, prior_loc, prior_sd)
         iwae_reduce([lw], out=ll[b0:b1])
     return -ll.sum()
+
+
+# =====================================================================================================
+# Gaussian-mixture EM (samplers.GaussianMixtureSampler)
+# =====================================================================================================
+def gmm_scratch(L, n_comp, device):
+    """The caller-owned scratch of the mvk_gmm_* entry points for (L, n_comp): its size does not depend on N."""
+    n = C.c_int64(0)
+    call("mvk_gmm_scratch_bytes", L, n_comp, C.byref(n))
+    return torch.empty((n.value + 7) // 8, dtype=torch.float64, device=device)
+
+
+def gmm_new_params(L, n_comp, device):
+    """Uninitialised parameter buffers of one mixture: weights [C], means [C,L], covs, cov_chol, prec_chol [C,L,L], logdet [C]."""
+    f = dict(dtype=torch.float32, device=device)
+    return dict(weights=torch.empty(n_comp, **f), means=torch.empty(n_comp, L, **f), covs=torch.empty(n_comp, L, L, **f),
+                cov_chol=torch.empty(n_comp, L, L, **f), prec_chol=torch.empty(n_comp, L, L, **f), logdet=torch.empty(n_comp, **f))
+
+
+def gmm_estep(x, p, resp, scratch, row_out=None, lb=None):
+    """resp [N,C] = responsibilities of the rows of x under the mixture p; row_out [N] = logsumexp rows, lb (1 double) = their
+    mean (mvk_gmm_estep, soft)."""
+    N, L = x.shape
+    call("mvk_gmm_estep", ptr(x), N, L, p["means"].shape[0], ptr(p["weights"]), ptr(p["means"]), ptr(p["prec_chol"]),
+         ptr(p["logdet"]), 0, ptr(resp), ptr(row_out), None, None, ptr(lb), ptr(scratch), stream_ptr())
+
+
+def gmm_estep_hard(x, means, resp, scratch, row_out=None, labels=None, changed=None):
+    """resp [N,C] = one-hot of the nearest of the rows of `means`; row_out [N] = that squared distance; labels [N] int32 in / out,
+    changed (1 int32) = rows whose label changed (mvk_gmm_estep, hard)."""
+    N, L = x.shape
+    call("mvk_gmm_estep", ptr(x), N, L, means.shape[0], None, ptr(means), None, None, 1, ptr(resp), ptr(row_out), ptr(labels),
+         ptr(changed), None, ptr(scratch), stream_ptr())
+
+
+def gmm_mstep(x, resp, p, reg_covar, scratch, means_only=False):
+    """The parameters p from the responsibilities (mvk_gmm_mstep); means_only: p["means"] alone (Lloyd's update)."""
+    N, L = x.shape
+    call("mvk_gmm_mstep", ptr(x), ptr(resp), N, L, p["means"].shape[0], float(reg_covar), int(means_only), ptr(p["weights"]),
+         ptr(p["means"]), ptr(p["covs"]), ptr(p["cov_chol"]), ptr(p["prec_chol"]), ptr(p["logdet"]), ptr(scratch), stream_ptr())
+
+
+def gmm_em_step(x, p, resp, state, reg_covar, tol, scratch):
+    """One guarded EM iteration on the device state block (mvk_gmm_em_step): a no-op once state says converged or failed."""
+    N, L = x.shape
+    call("mvk_gmm_em_step", ptr(x), N, L, p["means"].shape[0], float(reg_covar), float(tol), ptr(p["weights"]), ptr(p["means"]),
+         ptr(p["covs"]), ptr(p["cov_chol"]), ptr(p["prec_chol"]), ptr(p["logdet"]), ptr(resp), ptr(state), ptr(scratch),
+         stream_ptr())
+
+
+def gmm_new_state(device):
+    """The state block before the first step: lower bound -inf, everything else 0."""
+    st = torch.zeros(_lib.GMM_STATE_DOUBLES, dtype=torch.float64, device=device)
+    st[_lib.GMM_STATE["lb"]] = -math.inf
+    return st
+
+
+def gmm_sample(means, cov_chol, comp, eps):
+    """z [n,L] = means[comp] + cov_chol[comp] @ eps (mvk_gmm_sample); comp [n] int32."""
+    n, L = eps.shape
+    z = torch.empty_like(eps)
+    call("mvk_gmm_sample", ptr(means), ptr(cov_chol), ptr(comp), ptr(eps), n, L, means.shape[0], ptr(z), stream_ptr())
+    return z
