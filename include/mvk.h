@@ -920,6 +920,37 @@ int mvk_gmm_em_step(const float* X, int64_t N, int L, int C, double reg_covar, d
 int mvk_gmm_sample(const float* means, const float* cov_chol, const int32_t* comp, const float* eps, int64_t n, int L, int C,
                    float* z, void* stream);
 
+/* Image metrics of the evaluators (multivae/metrics/reconstruction/reconstruction.py: torchmetrics' StructuralSimilarityIndexMeasure
+ * and a torch sum of squared differences).  preds, target [B,C,H,W] fp32, contiguous.  The SSIM of one update ("Metrics"):
+ *   R = max(max preds - min preds, max target - min target) over the whole update, c1 = (0.01 R)^2, c2 = (0.03 R)^2;
+ *   g[i] ~ exp(-((i - 5) / 1.5)^2 / 2), 11 taps normalised to sum 1, the 2-D weight is the outer product, per channel;
+ *   only the (H - 10) x (W - 10) positions whose window lies inside the image; per position, with the weighted moments,
+ *   ssim = (2 mu_p mu_t + c1) (2 s_pt + c2) / ((mu_p^2 + mu_t^2 + c1) (s_p^2 + s_t^2 + c2)), variances not clamped;
+ *   ssim_rows[b] = the mean over the C (H - 10) (W - 10) positions of image b.  R = 0 gives NaN, and NaN propagates.
+ * Arithmetic is fp32 with every variance and covariance centred on the local mean (no E[x^2] - mu^2); sums over positions, pixels
+ * and rows are fp64 in a fixed order: two runs are bit-identical.
+ * mvk_ssim_tile: the tile edge, in window positions, of the rows kernel (images of any H, W >= 11 are tiled).
+ * mvk_ssim_scratch_bytes: the caller-owned scratch (8-byte aligned) of mvk_ssim_range and mvk_ssim_rows for that shape.
+ * mvk_ssim_range: range[0] (DEVICE float) = R of the n elements of preds and of target; a NaN element gives NaN.  The scratch of
+ *   any valid shape is large enough.
+ * mvk_ssim_rows: ssim_rows [B] and sse_rows [B] (sse_rows[b] = sum over image b of (preds - target)^2).  R is read from range_dev
+ *   (DEVICE float) unless that is NULL: then range_val is R.  mse_only != 0 writes sse_rows alone, reads neither range nor
+ *   scratch nor ssim_rows (all may be NULL / 0), forms no window and takes any H, W >= 1: a [B, D] batch is C = H = 1, W = D.
+ * mvk_ssim_accumulate: acc (DEVICE, MVK_SSIM_ACC_DOUBLES doubles) += {sum of ssim_rows, sum of sse_rows, B}, the rows added in
+ *   index order in fp64; ssim_rows may be NULL (the SSIM sum is left alone).
+ * MVK_EINVAL: a NULL pointer that is read or written, B or C <= 0, n <= 0, H or W < 11 (< 1 with mse_only), a grid of more than
+ * 2^31 - 1 tiles. */
+#define MVK_SSIM_ACC_SSIM 0
+#define MVK_SSIM_ACC_SSE 1
+#define MVK_SSIM_ACC_ROWS 2
+#define MVK_SSIM_ACC_DOUBLES 3
+int mvk_ssim_tile(void);
+int mvk_ssim_scratch_bytes(int B, int C, int H, int W, int64_t* bytes);
+int mvk_ssim_range(const float* preds, const float* target, int64_t n, float* range, void* scratch, void* stream);
+int mvk_ssim_rows(const float* preds, const float* target, int B, int C, int H, int W, const float* range_dev, float range_val,
+                  int mse_only, float* ssim_rows, float* sse_rows, void* scratch, void* stream);
+int mvk_ssim_accumulate(const float* ssim_rows, const float* sse_rows, int B, double* acc, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -209,9 +209,16 @@ PROTOTYPES = {
     "mvk_gmm_mstep": [_p, _p, _i64, _i, _i, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p],
     "mvk_gmm_em_step": [_p, _i64, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "mvk_gmm_sample": [_p, _p, _p, _p, _i64, _i, _i, _p, _p],
+    "mvk_ssim_tile": [],  # returns the tile edge, not a status
+    "mvk_ssim_scratch_bytes": [_i, _i, _i, _i, C.POINTER(C.c_int64)],
+    "mvk_ssim_range": [_p, _p, _i64, _p, _p, _p],
+    "mvk_ssim_rows": [_p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p, _p, _p],
+    "mvk_ssim_accumulate": [_p, _p, _i, _p, _p],
 }
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8
+SSIM_ACC = {"ssim": 0, "sse": 1, "rows": 2}  # MVK_SSIM_ACC_* (a block of 3 doubles)
+SSIM_ACC_DOUBLES = 3
 
 _lib = None
 

@@ -2585,3 +2585,61 @@ def gmm_sample(means, cov_chol, comp, eps):
     z = torch.empty_like(eps)
     call("mvk_gmm_sample", ptr(means), ptr(cov_chol), ptr(comp), ptr(eps), n, L, means.shape[0], ptr(z), stream_ptr())
     return z
+
+
+# =====================================================================================================
+# SSIM / squared error of image batches (metrics.Reconstruction)
+# =====================================================================================================
+def ssim_tile():
+    """The tile edge, in window positions, of the SSIM rows kernel (mvk_ssim_tile)."""
+    return _lib.load().mvk_ssim_tile()
+
+
+def ssim_scratch(B, Cc, H, W, device):
+    """The caller-owned scratch of ssim_range / ssim_rows for a [B,Cc,H,W] update (mvk_ssim_scratch_bytes)."""
+    n = C.c_int64(0)
+    call("mvk_ssim_scratch_bytes", B, Cc, H, W, C.byref(n))
+    return torch.empty((n.value + 7) // 8, dtype=torch.float64, device=device)
+
+
+def ssim_new_acc(device):
+    """The running {ssim_sum, sse_sum, rows} block of ssim_accumulate, zeroed."""
+    return torch.zeros(_lib.SSIM_ACC_DOUBLES, dtype=torch.float64, device=device)
+
+
+def ssim_range(preds, target, scratch, out=None):
+    """The data range R of one update as a 1-element device tensor (mvk_ssim_range): no host read."""
+    out = torch.empty(1, dtype=torch.float32, device=preds.device) if out is None else out
+    call("mvk_ssim_range", ptr(preds), ptr(target), preds.numel(), ptr(out), ptr(scratch), stream_ptr())
+    return out
+
+
+def ssim_rows(preds, target, scratch, data_range=None, ssim_out=None, sse_out=None):
+    """Per-image SSIM [B] and per-image sum of squared differences [B] of preds, target [B,Cc,H,W] (mvk_ssim_rows).  data_range:
+    a 1-element device tensor (read on the device), a Python float (passed by value), or None (ssim_range is run first)."""
+    B, Cc, H, W = preds.shape
+    f = dict(dtype=torch.float32, device=preds.device)
+    ssim_out = torch.empty(B, **f) if ssim_out is None else ssim_out
+    sse_out = torch.empty(B, **f) if sse_out is None else sse_out
+    if data_range is None:
+        data_range = ssim_range(preds, target, scratch)
+    by_value = not torch.is_tensor(data_range)
+    call("mvk_ssim_rows", ptr(preds), ptr(target), B, Cc, H, W, None if by_value else ptr(data_range),
+         float(data_range) if by_value else 0.0, 0, ptr(ssim_out), ptr(sse_out), ptr(scratch), stream_ptr())
+    return ssim_out, sse_out
+
+
+def sse_rows(preds, target, sse_out=None):
+    """Per-row sum of squared differences [B] of two [B, ...] tensors: the window-free path of mvk_ssim_rows."""
+    B = preds.shape[0]
+    if preds.numel() // B >= 2 ** 31:
+        raise _lib.MvkError("sse_rows: rows of 2^31 elements or more")
+    sse_out = torch.empty(B, dtype=torch.float32, device=preds.device) if sse_out is None else sse_out
+    call("mvk_ssim_rows", ptr(preds), ptr(target), B, 1, 1, preds.numel() // B, None, 0.0, 1, None, ptr(sse_out), None,
+         stream_ptr())
+    return sse_out
+
+
+def ssim_accumulate(acc, sse, ssim=None):
+    """acc += {sum of ssim, sum of sse, rows} in index order in fp64 on the device (mvk_ssim_accumulate)."""
+    call("mvk_ssim_accumulate", ptr(ssim), ptr(sse), sse.shape[0], ptr(acc), stream_ptr())
