@@ -199,7 +199,8 @@ int mvk_kl_gauss_bwd(const float* mean, int64_t n_mean, const float* lv, int64_t
                      const float* plv, int64_t n_plv, int64_t rows, int L, const float* g, float* dmean, float* dlv,
                      float* dpmean, float* dplv, void* stream) {
   if (rows == 0) return MVK_OK;
-  if (!mean || !lv || !pmean || !plv || !g || rows < 0 || L < 1) return MVK_EINVAL;
+  if (!mean || !lv || !pmean || !plv || !g || rows < 0 || L < 1 || n_mean < 1 || n_lv < 1 || n_pmean < 1 || n_plv < 1)
+    return MVK_EINVAL;  // the kernel indexes every operand modulo its count
   hipLaunchKernelGGL(kl_bwd_kernel, dim3(blocks_for(rows * L)), dim3(256), 0, mvk_stream(stream), mean, (long long)n_mean,
                      lv, (long long)n_lv, pmean, (long long)n_pmean, plv, (long long)n_plv, (long long)rows, L, g, dmean,
                      dlv, dpmean, dplv);
