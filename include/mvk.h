@@ -920,6 +920,47 @@ int mvk_gmm_em_step(const float* X, int64_t N, int L, int C, double reg_covar, d
 int mvk_gmm_sample(const float* means, const float* cov_chol, const int32_t* comp, const float* eps, int64_t n, int L, int C,
                    float* z, void* stream);
 
+/* Batched k-means for the Clustering evaluator (multivae/metrics/latent_clustering/clustering_class.py:54-110 fits scikit-learn's
+ * KMeans on a host copy of the training embeddings once per run, votes a class per cluster and classifies the test embeddings on
+ * the host).  R independent fits of K centres on the SAME rows advance together: X [N,L] rows, centers [R,K,L], labels [R,N] int32,
+ * all caller-owned.  The squared distance of a row is fp32 and direct (d = x - c, fmaf(d, d, .) in index order, never
+ * |x|^2 - 2 x.c + |c|^2), the label is its first minimum; every sum over rows is fp64 from the first addend on, in a fixed order
+ * (per thread, per workgroup, across workgroups through `scratch`: mvk_kmeans_scratch_bytes(L, K, R) bytes, independent of N,
+ * 8-byte aligned); counts are integers (integer atomics); there is no floating-point atomic.  Bit-reproducible, and the bits of
+ * run r do not depend on R.  1 <= L <= 64, 1 <= K <= 64, 1 <= R <= 32 (else MVK_EINVAL); N = 0 is MVK_OK and writes nothing; K > N
+ * is legal.
+ * mvk_kmeans_assign: labels (nullable) = argmin_k |x_n - c_rk|^2, d2 [R,N] (nullable) = that minimum, inertia [R] (nullable, DEVICE
+ *   doubles, needs scratch) = its fp64 sum over the rows.  With y [N] int32 and table [R,K,n_classes+1] int64: table[r, label, y]
+ *   += 1, a y outside [0, n_classes) counted in the extra last column (ACCUMULATED: the caller zeroes it; 1 <= n_classes <= 2^24).
+ *   With y, majority [R,K] int32 and correct [R] int64: correct[r] += rows with majority[r, label] == y (ACCUMULATED).  One call
+ *   serves the k-means++ distances, the final relabelling, the training contingency table and the test scoring.
+ * mvk_kmeans_step: one iteration of scikit-learn's _kmeans_single_lloyd for every run whose CONVERGED is 0: labels from the current
+ *   centres, new centre of a cluster = its fp64 row sum / its count stored as fp32, the centres are replaced, then on the run's block
+ *   of `state` (DEVICE, [R, MVK_KMEANS_STATE_DOUBLES] doubles; the caller zeroes it and sets labels to -1 before the first step):
+ *   ITER += 1, CHANGED = rows whose label changed, INERTIA = sum of the row minima (w.r.t. the centres the labels were taken from),
+ *   SHIFT = sum (new - old)^2 over the stored centres, EMPTY += clusters without a row, CONVERGED = 1 when CHANGED is 0 (strict),
+ *   else 2 when SHIFT <= *tol (tol: DEVICE double, so that the caller never synchronises to compute it).  A run whose CONVERGED
+ *   is non-zero is untouched by further steps (centres, labels and state keep their bits), so the host may enqueue several steps
+ *   and read the block once.  DEVIATION from scikit-learn: a cluster without rows keeps its previous centre and is counted in
+ *   EMPTY; scikit-learn moves it to the row farthest from its own centre (a per-run top-k over the rows, for a path that
+ *   well-seeded fits rarely take).
+ * mvk_kmeans_vote: majority[r, k] = first maximum of table[r, k, 0 .. n_classes) (np.bincount(...).argmax(): ties go to the smallest
+ *   class); a cluster with no row in a real class maps to its own index k (the reference's default entry of labels_dict). */
+#define MVK_KMEANS_STATE_ITER 0
+#define MVK_KMEANS_STATE_CONVERGED 1
+#define MVK_KMEANS_STATE_SHIFT 2
+#define MVK_KMEANS_STATE_CHANGED 3
+#define MVK_KMEANS_STATE_INERTIA 4
+#define MVK_KMEANS_STATE_EMPTY 5
+#define MVK_KMEANS_STATE_DOUBLES 8
+int mvk_kmeans_scratch_bytes(int L, int K, int R, int64_t* bytes);
+int mvk_kmeans_assign(const float* X, int64_t N, int L, int K, int R, const float* centers, int32_t* labels, float* d2,
+                      const int32_t* y, int n_classes, int64_t* table, const int32_t* majority, int64_t* correct, double* inertia,
+                      void* scratch, void* stream);
+int mvk_kmeans_step(const float* X, int64_t N, int L, int K, int R, const double* tol, float* centers, int32_t* labels,
+                    double* state, void* scratch, void* stream);
+int mvk_kmeans_vote(const int64_t* table, int R, int K, int n_classes, int32_t* majority, void* stream);
+
 /* Image metrics of the evaluators (multivae/metrics/reconstruction/reconstruction.py: torchmetrics' StructuralSimilarityIndexMeasure
  * and a torch sum of squared differences).  preds, target [B,C,H,W] fp32, contiguous.  The SSIM of one update ("Metrics"):
  *   R = max(max preds - min preds, max target - min target) over the whole update, c1 = (0.01 R)^2, c2 = (0.03 R)^2;

@@ -214,11 +214,19 @@ PROTOTYPES = {
     "mvk_ssim_range": [_p, _p, _i64, _p, _p, _p],
     "mvk_ssim_rows": [_p, _p, _i, _i, _i, _i, _p, _f, _i, _p, _p, _p, _p],
     "mvk_ssim_accumulate": [_p, _p, _i, _p, _p],
+    "mvk_kmeans_scratch_bytes": [_i, _i, _i, C.POINTER(C.c_int64)],
+    "mvk_kmeans_assign": [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p],
+    "mvk_kmeans_step": [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "mvk_kmeans_vote": [_p, _i, _i, _i, _p, _p],
 }
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8
 SSIM_ACC = {"ssim": 0, "sse": 1, "rows": 2}  # MVK_SSIM_ACC_* (a block of 3 doubles)
 SSIM_ACC_DOUBLES = 3
+# MVK_KMEANS_STATE_* (a block of 8 doubles per run)
+KMEANS_STATE = {"iter": 0, "converged": 1, "shift": 2, "changed": 3, "inertia": 4, "empty": 5}
+KMEANS_STATE_DOUBLES = 8
+KMEANS_MAX_RUNS = 32  # runs of one mvk_kmeans_* call
 
 _lib = None
 

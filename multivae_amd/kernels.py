@@ -2588,6 +2588,47 @@ def gmm_sample(means, cov_chol, comp, eps):
 
 
 # =====================================================================================================
+# Batched k-means (metrics.Clustering)
+# =====================================================================================================
+def kmeans_scratch(L, n_clusters, n_runs, device):
+    """The caller-owned scratch of the mvk_kmeans_* entry points for (L, n_clusters, n_runs): its size does not depend on N."""
+    n = C.c_int64(0)
+    call("mvk_kmeans_scratch_bytes", L, n_clusters, n_runs, C.byref(n))
+    return torch.empty((n.value + 7) // 8, dtype=torch.float64, device=device)
+
+
+def kmeans_new_state(n_runs, device):
+    """The state blocks [R, 8] before the first step: all 0 (the labels of the first step are -1)."""
+    return torch.zeros(n_runs, _lib.KMEANS_STATE_DOUBLES, dtype=torch.float64, device=device)
+
+
+def kmeans_assign(x, centers, scratch=None, labels=None, d2=None, y=None, n_classes=0, table=None, majority=None, correct=None,
+                  inertia=None):
+    """Nearest centre of every row of x [N,L] for every run of centers [R,K,L] (mvk_kmeans_assign): labels [R,N] int32, d2 [R,N],
+    inertia [R] float64 (needs scratch); with y [N] int32: table [R,K,n_classes+1] int64 += the contingency counts, correct [R]
+    int64 += rows with majority[r, label] == y.  Every output is optional."""
+    N, L = x.shape
+    R, K, _ = centers.shape
+    call("mvk_kmeans_assign", ptr(x), N, L, K, R, ptr(centers), ptr(labels), ptr(d2), ptr(y), int(n_classes), ptr(table),
+         ptr(majority), ptr(correct), ptr(inertia), ptr(scratch), stream_ptr())
+
+
+def kmeans_step(x, tol, centers, labels, state, scratch):
+    """One guarded Lloyd iteration of every run (mvk_kmeans_step): a no-op for a run whose state says converged.  tol is a DEVICE
+    float64 scalar."""
+    N, L = x.shape
+    R, K, _ = centers.shape
+    call("mvk_kmeans_step", ptr(x), N, L, K, R, ptr(tol), ptr(centers), ptr(labels), ptr(state), ptr(scratch), stream_ptr())
+
+
+def kmeans_vote(table, majority):
+    """majority [R,K] int32 = the first maximum of table [R,K,n_classes+1] over the real classes; a cluster without a row in one
+    maps to its own index (mvk_kmeans_vote)."""
+    R, K, C1 = table.shape
+    call("mvk_kmeans_vote", ptr(table), R, K, C1 - 1, ptr(majority), stream_ptr())
+
+
+# =====================================================================================================
 # SSIM / squared error of image batches (metrics.Reconstruction)
 # =====================================================================================================
 def ssim_tile():

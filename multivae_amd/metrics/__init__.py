@@ -1,8 +1,10 @@
 """Evaluators of a trained model (`multivae/metrics`): joint likelihoods, reconstruction error (SSIM / MSE, on the fused kernel of
-csrc/ssim.hip) and cross-modal / joint coherences.  FIDEvaluator (needs Inception weights), Visualization (torchvision, PIL),
-Clustering and ClassifierPolyMNIST are not built."""
+csrc/ssim.hip), cross-modal / joint coherences and the k-means accuracy of the latent space (Clustering, on the batched k-means of
+csrc/kmeans.hip).  FIDEvaluator (needs Inception weights), Visualization (torchvision, PIL) and ClassifierPolyMNIST are not
+built."""
 from .base import Evaluator, EvaluatorConfig
 from .coherences import CoherenceEvaluator, CoherenceEvaluatorConfig
+from .latent_clustering import Clustering, ClusteringConfig
 from .likelihoods import LikelihoodsEvaluator, LikelihoodsEvaluatorConfig
 from .reconstruction import Reconstruction, ReconstructionConfig
 
@@ -16,3 +18,5 @@ __all__ = [
     "CoherenceEvaluator",
     "CoherenceEvaluatorConfig",
 ]
+# Clustering and ClusteringConfig are importable from here; __all__ (the star-import surface) stays the set that
+# tests/test_metrics_host.py::test_package_surface pins.
