@@ -992,6 +992,40 @@ int mvk_ssim_rows(const float* preds, const float* target, int B, int C, int H, 
                   int mse_only, float* ssim_rows, float* sse_rows, void* scratch, void* stream);
 int mvk_ssim_accumulate(const float* ssim_rows, const float* sse_rows, int B, double* acc, void* stream);
 
+/* Frechet statistics for the FIDEvaluator (multivae/metrics/fids/fids.py:112-156 keeps every batch's activations in a list,
+ * copies all of them to the host and takes np.mean and np.cov there).  Two feature streams of width D (stream 0 = real data X0,
+ * stream 1 = generated data X1; [n, D] fp32 rows, contiguous) are folded batch by batch into a caller-owned `state` (DEVICE,
+ * mvk_fd_state_bytes(D) bytes, 8-byte aligned) that holds per stream a shift c[D] (fp32), the row count (int64),
+ * S1[D] = sum (x - c) and S2 = sum (x - c)(x - c)^T (fp64; only the mvk_fd_tile() x mvk_fd_tile() tiles on or above the diagonal
+ * are computed and stored).  c is the column mean of the stream's FIRST batch and never changes: features far from zero lose
+ * their covariance to cancellation in un-shifted fp32 raw moments.  Within a call x - c is fp32, the rows are walked in chunks of
+ * mvk_fd_chunk() rows, the chunk's (X - c)^T (X - c) is formed with the f32-input MFMA (bit for bit a row-ordered fmaf chain) and
+ * every chunk is added to fp64; S1 is fp64 from the first addend on.  A state element is written by exactly one workgroup per
+ * launch and there is no floating-point atomic: the same sequence of calls gives the same bits.  Any D >= 1 up to 65535 tiles per
+ * edge, any n >= 1.
+ * mvk_fd_tile / mvk_fd_chunk: the tile edge of S2 and the rows per chunk (not statuses).
+ * mvk_fd_state_bytes: the size of `state` for two streams.
+ * mvk_fd_begin: zeroes the state and sets each stream's shift to the column mean of its n rows (rows added in row order in fp64,
+ *   stored as fp32).  It adds no row: the caller follows it with mvk_fd_update on the same batch.  X1 may be NULL: stream 1 is
+ *   left empty with a zero shift.
+ * mvk_fd_update: adds the n rows of X0 to stream 0 and, unless X1 is NULL, the n rows of X1 to stream 1, in one launch.
+ * mvk_fd_finish: mean [2,D] fp64 = c + S1 / n; cov [2,D,D] fp64 = (S2 - S1 S1^T / n) / (n - 1), the full matrix, the lower
+ *   triangle mirrored bit for bit from the upper (np.cov(rowvar=False); n = 1 gives NaN as numpy does, an empty stream NaN);
+ *   terms (MVK_FD_TERMS doubles) = {|mean0 - mean1|^2, tr cov0, tr cov1, n0, n1}.  The state is left as it was.
+ * MVK_EINVAL: D < 1 or too large, n < 1, X0 or state NULL, a NULL output. */
+#define MVK_FD_TERM_DMEAN2 0
+#define MVK_FD_TERM_TRACE0 1
+#define MVK_FD_TERM_TRACE1 2
+#define MVK_FD_TERM_N0 3
+#define MVK_FD_TERM_N1 4
+#define MVK_FD_TERMS 5
+int mvk_fd_tile(void);
+int mvk_fd_chunk(void);
+int mvk_fd_state_bytes(int D, int64_t* bytes);
+int mvk_fd_begin(const float* X0, const float* X1, int64_t n, int D, void* state, void* stream);
+int mvk_fd_update(const float* X0, const float* X1, int64_t n, int D, void* state, void* stream);
+int mvk_fd_finish(void* state, int D, double* mean, double* cov, double* terms, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -218,6 +218,12 @@ PROTOTYPES = {
     "mvk_kmeans_assign": [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p],
     "mvk_kmeans_step": [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "mvk_kmeans_vote": [_p, _i, _i, _i, _p, _p],
+    "mvk_fd_tile": [],  # returns the tile edge, not a status
+    "mvk_fd_chunk": [],  # returns the rows per chunk, not a status
+    "mvk_fd_state_bytes": [_i, C.POINTER(C.c_int64)],
+    "mvk_fd_begin": [_p, _p, _i64, _i, _p, _p],
+    "mvk_fd_update": [_p, _p, _i64, _i, _p, _p],
+    "mvk_fd_finish": [_p, _i, _p, _p, _p, _p],
 }
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8
@@ -227,6 +233,8 @@ SSIM_ACC_DOUBLES = 3
 KMEANS_STATE = {"iter": 0, "converged": 1, "shift": 2, "changed": 3, "inertia": 4, "empty": 5}
 KMEANS_STATE_DOUBLES = 8
 KMEANS_MAX_RUNS = 32  # runs of one mvk_kmeans_* call
+FD_TERM = {"dmean2": 0, "trace0": 1, "trace1": 2, "n0": 3, "n1": 4}  # MVK_FD_TERM_* (a block of 5 doubles)
+FD_TERMS = 5
 
 _lib = None
 

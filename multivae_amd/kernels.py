@@ -2684,3 +2684,47 @@ def sse_rows(preds, target, sse_out=None):
 def ssim_accumulate(acc, sse, ssim=None):
     """acc += {sum of ssim, sum of sse, rows} in index order in fp64 on the device (mvk_ssim_accumulate)."""
     call("mvk_ssim_accumulate", ptr(ssim), ptr(sse), sse.shape[0], ptr(acc), stream_ptr())
+
+
+# =====================================================================================================
+# Streaming Frechet statistics (metrics.FIDEvaluator)
+# =====================================================================================================
+def fd_tile():
+    """The tile edge of the second-moment matrix of the Frechet-statistics kernel (mvk_fd_tile)."""
+    return _lib.load().mvk_fd_tile()
+
+
+def fd_chunk():
+    """The rows of a call that the Frechet-statistics kernel walks at a time (mvk_fd_chunk)."""
+    return _lib.load().mvk_fd_chunk()
+
+
+def fd_new_state(D, device):
+    """The caller-owned state of the mvk_fd_* entry points for two streams of width D (mvk_fd_state_bytes); fd_begin zeroes it."""
+    n = C.c_int64(0)
+    call("mvk_fd_state_bytes", D, C.byref(n))
+    return torch.empty((n.value + 7) // 8, dtype=torch.float64, device=device)
+
+
+def fd_begin(state, x0, x1=None):
+    """Zero the state and set each stream's shift to the column mean of its rows (mvk_fd_begin): x0, x1 [n,D] fp32 are the FIRST
+    batch of the real and of the generated stream; no row is added.  x1 = None leaves stream 1 empty."""
+    n, D = x0.shape
+    call("mvk_fd_begin", ptr(x0), ptr(x1), n, D, ptr(state), stream_ptr())
+
+
+def fd_update(state, x0, x1=None):
+    """Add the n rows of x0 to stream 0 and of x1 (unless None) to stream 1 in one launch (mvk_fd_update): no host read."""
+    n, D = x0.shape
+    call("mvk_fd_update", ptr(x0), ptr(x1), n, D, ptr(state), stream_ptr())
+
+
+def fd_finish(state, D, mean=None, cov=None, terms=None):
+    """mean [2,D], cov [2,D,D] (np.cov(rowvar=False), exactly symmetric) and terms [5] = {|mean0 - mean1|^2, tr cov0, tr cov1,
+    n0, n1}, all float64 on the device (mvk_fd_finish); the state is left as it was."""
+    f = dict(dtype=torch.float64, device=state.device)
+    mean = torch.empty(2, D, **f) if mean is None else mean
+    cov = torch.empty(2, D, D, **f) if cov is None else cov
+    terms = torch.empty(_lib.FD_TERMS, **f) if terms is None else terms
+    call("mvk_fd_finish", ptr(state), D, ptr(mean), ptr(cov), ptr(terms), stream_ptr())
+    return mean, cov, terms
