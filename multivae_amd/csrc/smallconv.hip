@@ -1514,9 +1514,13 @@ static size_t bwd_lds(int h, int w) {
   return fl * sizeof(float);
 }
 
+// h, w <= 16: the per-thread staging of the halo tile is sized for (2 h + 2)(2 w + 2) <= 34 * 34 elements per channel (ND of
+// small_down_fwd_kernel and small_up_bwd_kernel).  An elongated map with the same position count (4 x 64: 10 * 130 = 1300 per
+// channel) would leave the tail of the tile unstaged and the MFMA phase reading LDS nobody wrote, without any fault; such shapes
+// go to smallcin / the tiled engine.
 static bool supported(int h, int w, int Cu, int Cv) {
   const int P = h * w;
-  return Cu >= 1 && Cu <= 4 && (Cv == 16 || Cv == 32 || Cv == 64) && P % 64 == 0 && P <= 256;
+  return Cu >= 1 && Cu <= 4 && (Cv == 16 || Cv == 32 || Cv == 64) && P % 64 == 0 && P <= 256 && h <= 16 && w <= 16;
 }
 
 template <int CU, int CV>

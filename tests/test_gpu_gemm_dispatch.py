@@ -616,6 +616,45 @@ def p_conv_wgrad(seed, n, h, w, Cu, Cv, u_nchw=False, u_act=NONE, ws="ws", defer
                 keep=[Ud, Vd, usd])
 
 
+PAIR = ((8, 32, 64), (4, 64, 128))  # (h = w, Cu, Cv) of the SVHN encoder's two inner layers (models/nn/svhn.py)
+# Smallest batch mvk_conv4s2_wgrad_pair takes as one launch (igemm.hip: z > 1 and tiles * z >= bf_min_blocks() = 256 for BOTH
+# layers, slices of an even number of 16-wide k-tiles, split target SPLITK_C4 = 256):
+#   32 -> 64 at 8x8:   M = 512, N = 64: 4 tiles, 4 n k-tiles, <= 64 slices of >= 2 k-tiles: z = 2 n >= 64  <=>  n >= 32 (n = 31: 248 blocks)
+#   64 -> 128 at 4x4:  M = 1024, N = 128: 16 tiles, n k-tiles, <= 16 slices of >= 2: z = ceil(n / 2) >= 16  <=>  n >= 31
+PAIR_N = 32
+PAIRK = "igemm_bf_pair_kernel<128,64,4,2,false,2>"
+
+
+def p_conv_wgrad_pair(seed, n, deferred=True, single=False):
+    """mvk_conv4s2_wgrad_pair: the weight gradients of two NHWC layers at one batch, dW0 / dW1 [Cv][Cu][4][4] +=.  single: the same
+    two gradients by two mvk_conv4s2_wgrad calls."""
+    from multivae_amd._lib import call, ptr, stream_ptr
+
+    gn = g(seed)
+    d = dev()
+    outs, ops = [], []
+    for h, Cu, Cv in PAIR:
+        U, _ = _conv_inputs(gn, n, h, h, Cu, Cv)
+        V = torch.randn(n, Cv, h, h, generator=gn) * (torch.rand(1, Cv, 1, 1, generator=gn) + 0.5) / math.sqrt(n * h * h)
+        f = lambda Ux, Vx, s_=(Cv, Cu, 4, 4): torch.nn.grad.conv2d_weight(Ux, s_, Vx, stride=2, padding=1)  # noqa: E731
+        init = torch.randn(Cv, Cu, 4, 4, generator=gn)
+        outs.append(Out(f(U.double(), V.double()), f(U.double().abs(), V.double().abs()) + init.double().abs(),
+                        f(two_piece(U), two_piece(V)), init=init))
+        ops.append((_nhwc(U).to(d), _nhwc(V).to(d), h, Cu, Cv))
+    wsp, wsn = WS("ws")
+
+    def run(bufs):
+        (U0, V0, h0, a0, b0), (U1, V1, h1, a1, b1) = ops
+        if single:
+            for (U_, V_, h_, a_, b_), buf in zip(ops, bufs):
+                call("mvk_conv4s2_wgrad", ptr(U_), ptr(V_), ptr(buf), n, h_, h_, a_, b_, 0, None, NONE, wsp, wsn, stream_ptr())
+        else:
+            call("mvk_conv4s2_wgrad_pair", ptr(U0), ptr(V0), ptr(bufs[0]), h0, h0, a0, b0, ptr(U1), ptr(V1), ptr(bufs[1]), h1, h1, a1,
+                 b1, n, wsp, wsn, stream_ptr())
+
+    return Prep(run, outs, deferred=deferred, flags=TILED_ONLY, keep=ops)
+
+
 def p_unflatten(seed, n, Cin, Cout):
     """mvk_unflatten_wgrad: dWref [Cin][Cout][4][4] += Z^T dY, dY [n][(tap, co)]."""
     from multivae_amd._lib import call, ptr, stream_ptr
@@ -867,6 +906,15 @@ CASES += [
          [bf(128, 64, "COL", "N"), BATCH], [fast(64, 64, 32, "COL", "N"), BATCH], "deferred slabs"),
     case("wgrad-noscratch-atomic", p_conv_wgrad, dict(n=64, h=4, w=4, Cu=64, Cv=128, ws="none"),
          [bf(128, 64, "COL", "N")], [fast(64, 64, 32, "COL", "N")], "fp32-atomic split K"),
+    case("wgradpair-bfpair128x64-col-deferred", p_conv_wgrad_pair, dict(n=PAIR_N),
+         [PAIRK, BATCH], [fast(64, 64, 32, "COL", "N"), BATCH],
+         "both layers split into >= 256 blocks of the 128x64 split-bf16 tile, gradients in the arena: ONE launch (igemm.hip "
+         "mvk_conv4s2_wgrad_pair); f32 engine: two launches"),
+    case("wgradpair-notdeferred-two-launches", p_conv_wgrad_pair, dict(n=PAIR_N, deferred=False),
+         [bf(128, 64, "COL", "N"), RED], [fast(64, 64, 32, "COL", "N"), RED], "no arena: two mvk_conv4s2_wgrad launches"),
+    case("wgradpair-below-n-two-launches", p_conv_wgrad_pair, dict(n=PAIR_N - 1),
+         [bf(128, 64, "COL", "N"), fast(64, 64, 32, "COL", "N"), BATCH], [fast(64, 64, 32, "COL", "N"), BATCH],
+         "n = 31: 4 tiles x 62 slices = 248 < 256 blocks at 32 -> 64 channels -> two launches (the first on the exact-fp32 tile)"),
     case("unflatten-bf128x64-plainR-bmN-Eunflatref", p_unflatten, dict(n=512, Cin=20, Cout=64),
          [bf(128, 64, "R", "N"), RED], [fast(64, 64, 32, "R", "N"), RED], "E_UNFLATREF, 16 tiles x 16 slices"),
     case("flatten-bf128x32-plainR-bmN-Econvref16", p_flatten, dict(n=512, Cu=64, Cv=20),
@@ -989,6 +1037,22 @@ def check_case(c, engine_f32=F32_ENGINE, collect=False):
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
 def test_dispatch_leaf(c):
     check_case(c)
+
+
+def test_wgrad_pair_matches_two_launches():
+    """igemm.hip's contract of mvk_conv4s2_wgrad_pair: same slabs, same sums as two mvk_conv4s2_wgrad launches under the same arena,
+    so both gradients are bit-identical; without an arena the call is those two launches (ordered scratch slabs, the same bits)."""
+    seed = 20231
+    runs = {}
+    for name, kw in (("pair", {}), ("single", dict(single=True)), ("plain", dict(deferred=False))):
+        bufs, run = execute(p_conv_wgrad_pair(seed, PAIR_N, **kw))
+        runs[name] = (launched_kernels(run), [b.clone() for b in bufs])
+    if not F32_ENGINE:
+        assert runs["pair"][0] == sorted([PAIRK, BATCH]) and runs["single"][0] == sorted([bf(128, 64, "COL", "N"), BATCH])
+        assert runs["plain"][0] == sorted([bf(128, 64, "COL", "N"), RED])
+    for i in range(2):
+        assert torch.equal(runs["pair"][1][i], runs["single"][1][i]), f"dW{i}: pair vs two launches under the arena"
+        assert torch.equal(runs["pair"][1][i], runs["plain"][1][i]), f"dW{i}: pair vs the not-deferred call"
 
 
 def test_case_ids_are_unique():
