@@ -299,28 +299,38 @@ int conv3_smallcout(const float* X, const float* Wp, const float* bias, float* Y
   return MVK_OK;
 }
 
+// Workgroups (= slab rows of 9 * Cin * Cout floats) conv3_small_wgrad uses for this problem when the scratch holds them all; 0: shape
+// not covered.  Every condition of the launch except the scratch itself: a caller reserves scratch only behind this test.
+int conv3_small_wgrad_slabs(const float* X, const float* dY, int n, int H, int W, int Cin, int Cout) {
+  static const int off = mvk_tune("MVK_CONV3SMALL") ? atoi(mvk_tune("MVK_CONV3SMALL")) == 0 : 0;
+  const bool in_small = Cin <= 4, out_small = Cout <= 4;
+  if (off || n < 1 || (!in_small && !out_small) || W > 256) return 0;
+  const int CS = in_small ? Cin : Cout, CB = in_small ? Cout : Cin;
+  const int CG = CB / 4;
+  if (CB % 4 != 0 || CG < 1 || CG > 64 || (64 % CG) != 0) return 0;  // CB in {4, 8, 16, 32, 64, 128, 256}
+  if (!mvk_aligned16(in_small ? dY : X)) return 0;
+  const size_t tile = ((size_t)(C3_RB + 2) * (W + 2) * CS + 3) & ~(size_t)3;
+  if ((tile + (size_t)(64 / CG) * 9 * Cin * Cout) * sizeof(float) > 64 * 1024) return 0;
+  const long long items = (long long)n * ((H + C3_RB - 1) / C3_RB);
+  return (int)(items > C3_WGRAD_SLABS ? C3_WGRAD_SLABS : items);
+}
+
 // slab: [*nz][9 * Cin * Cout] partial gradients already in dWref order; 1: shape not covered
 int conv3_small_wgrad(const float* X, const float* dY, float* slab, long long slab_floats, int n, int H, int W, int Cin, int Cout,
                       int* nz, hipStream_t s) {
-  static const int off = mvk_tune("MVK_CONV3SMALL") ? atoi(mvk_tune("MVK_CONV3SMALL")) == 0 : 0;
-  const bool in_small = Cin <= 4, out_small = Cout <= 4;
-  if (off || n < 1 || (!in_small && !out_small) || W > 256) return 1;
+  long long grid = conv3_small_wgrad_slabs(X, dY, n, H, W, Cin, Cout);
+  if (grid < 1 || !slab || !mvk_aligned16(slab)) return 1;
+  const bool in_small = Cin <= 4;
   const int CS = in_small ? Cin : Cout, CB = in_small ? Cout : Cin;
   const int CG = CB / 4;
-  if (CB % 4 != 0 || CG < 1 || CG > 64 || (64 % CG) != 0 || !slab) return 1;  // CB in {4, 8, 16, 32, 64, 128, 256}
   const float* S = in_small ? X : dY;
   const float* B = in_small ? dY : X;
-  if (!mvk_aligned16(B) || !mvk_aligned16(slab)) return 1;
   const long long total = 9ll * Cin * Cout;
-  const int bands = (H + C3_RB - 1) / C3_RB;
-  long long grid = (long long)n * bands;
-  if (grid > C3_WGRAD_SLABS) grid = C3_WGRAD_SLABS;
   if (grid * total > slab_floats) grid = slab_floats / total;
   if (grid < 1) return 1;
   C3WArgs a{S, B, slab, n, H, W, CB, in_small ? 1 : -1, in_small ? 1 : 0};
   const size_t tile = ((size_t)(C3_RB + 2) * (W + 2) * CS + 3) & ~(size_t)3;
   const size_t lds = (tile + (size_t)(64 / CG) * total) * sizeof(float);
-  if (lds > 64 * 1024) return 1;
   switch (CS) {
     case 1: hipLaunchKernelGGL(conv3_small_wgrad_kernel<1>, dim3((unsigned)grid), dim3(256), lds, s, a); break;
     case 2: hipLaunchKernelGGL(conv3_small_wgrad_kernel<2>, dim3((unsigned)grid), dim3(256), lds, s, a); break;

@@ -704,6 +704,7 @@ int conv3_smallcout(const float* X, const float* Wp, const float* bias, float* Y
                     const float* mask_src, int mask_act, hipStream_t s);
 int conv3_small_wgrad(const float* X, const float* dY, float* slab, long long slab_floats, int n, int H, int W, int Cin, int Cout,
                       int* nz, hipStream_t s);
+int conv3_small_wgrad_slabs(const float* X, const float* dY, int n, int H, int W, int Cin, int Cout);  // 0 = shape not covered
 // skinny.hip: few-row linear layer (a workgroup per 16 x 16 output tile, its waves split K): 1 = shape not covered
 int heads_launch(const float* X, const float* W0, const float* b0, float* Y0, const float* W1, const float* b1, float* Y1,
                  int M, int N, int K, long long w_sk, long long w_sn, int act, hipStream_t s, float* ws = nullptr,
@@ -1146,6 +1147,9 @@ static int conv3x3_any(const float* X, const float* Wp, const float* bias, float
     if (rc != 1) return rc;
     if (dpart) return MVK_EINVAL;  // covered shapes never decline after taking arena space
   }
+  // The tiled engine knows no input activation, pre_scale, operand bounds, published maximum or second store: a fused form the
+  // register-stationary kernels decline (a sigmoid as activation or mask) is refused, never computed without its options.
+  if (fused) return MVK_EINVAL;
   GemmDesc d{};
   d.a = AOperand{};
   d.a.p = X;
@@ -1288,16 +1292,21 @@ static int conv3x3_wgrad_any(const float* X, const float* dY, float* dWref, floa
                              int W, int Cin, int Cout, float* ws, int64_t ws_floats, void* stream, const float* x_amax,
                              const float* dy_amax) {
   if (!X || !dY || !dWref || n < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return MVK_EINVAL;
-  if (n > 0 && (Cin <= 4 || Cout <= 4)) {  // an image on one side: per-workgroup slabs in dWref order + ordered finish
+  // an image on one side: per-workgroup slabs in dWref order + ordered finish.  Arena space is reserved only behind the coverage
+  // test (a region that is never pushed stays taken until mvk_defer_end, and launch_splitk below reserves again), and only for the
+  // slabs the launch writes.
+  const int small_slabs = n > 0 && (Cin <= 4 || Cout <= 4) ? conv3_small_wgrad_slabs(X, dY, n, H, W, Cin, Cout) : 0;
+  if (small_slabs > 0) {
     const long long total = 9ll * Cin * Cout;
-    float* dslab = defer_scratch(dWref, 1024 * total, mvk_stream(stream));
+    float* dslab = defer_scratch(dWref, small_slabs * total, mvk_stream(stream));
     int nz = 0;
-    const int rc = conv3_small_wgrad(X, dY, dslab ? dslab : ws, dslab ? 1024 * total : ws_floats, n, H, W, Cin, Cout, &nz,
+    const int rc = conv3_small_wgrad(X, dY, dslab ? dslab : ws, dslab ? small_slabs * total : ws_floats, n, H, W, Cin, Cout, &nz,
                                      mvk_stream(stream));
     if (rc == MVK_OK)
       return dslab ? defer_push_plain(dWref, dslab, total, nz, total, mvk_stream(stream))
                    : colsum_finish_any(ws, nz, (int)total, dWref, mvk_stream(stream));
     if (rc != 1) return rc;
+    if (dslab) return MVK_EINVAL;  // covered shapes never decline after taking arena space
   }
   if (n > 0 && mvk_aligned16(X) && mvk_aligned16(dY) && c3rs_wgrad_covers(n, H, W, Cin, Cout)) {
     const int types = (Cin / 64) * (Cout / 64), workers = 256 / types;

@@ -28,6 +28,13 @@ accumulator chain (longer ones are split into slabs by the split-K form or the w
 operands are off by ~2^-17 per operand: the weakest per-entry rejection in the table is 1.2x the bound (column sums of 160
 terms), the aggregate ones 4-20x torch's error.
 
+The 3x3 / stride-1 routes of the engine (tw = 3, mul = 1 gather: AM_ROW forward / backward data, AM_COL weight gradient, E_CONVREF
+with taps = 9, the residual epilogue, fused column sums) are the `c3` cases; their references are tests/conv3_ref.py, and the
+entry-point wrappers p_conv3 / p_conv3_wgrad also serve the table of the specialised 3x3 kernels (tests/test_gpu_conv3x3.py).
+c3fwd-bf128x32-row-K2304 reduces 2304 terms in one chain, beyond the 1024 C_ENTRY was derived for.  Measured on an MI355X: 0.17x the
+bound on the split-bf16 engine and 0.28x on the exact-fp32 engine (two-piece emulation: 1.15x), so the case is held to (a) like every
+other one; profiles/NOTES_conv3.md also records the exact-fp32 engine against torch's fp32 GEMM there (2.2x its max error).
+
 The default configuration is the one under test (engine 1: split bf16).  test_engine_f32_child re-runs this table in a fresh
 process with MVK_ENGINE=f32 (the documented switch, read once per process), where each case expects its `f32` kernels.
 
@@ -695,6 +702,133 @@ def p_flatten(seed, n, Cu, Cv):
                 agg=lambda: lay((Hd.t() @ dyd).double()), keep=[Hd, dyd])
 
 
+# ---- 3x3 / stride 1 / pad 1 (tests/conv3_ref.py; tests/test_gpu_conv3x3.py holds the table of the specialised kernels) ----------------
+RS_ALL = 0x800  # mvk_debug_set_flags: the register-stationary 3x3 kernels take every problem size they cover
+
+
+def _out3(r, lay=lambda t: t, init=None, shape=None):
+    """Out of a conv_small_ref.Ref; degh = the second emulation (scaled fp16 pairs without a cross term) where it is defined."""
+    bound = lay(r.bound) if init is None else lay(r.bound) + init.double().abs()
+    o = Out(lay(r.ref), bound, lay(r.deg2), init=init, shape=shape)
+    o.degh = None if r.degh is None else lay(r.degh)
+    o.derived = False
+    return o
+
+
+def p_conv3(seed, n, H, W, Cin, Cout, entry="plain", bias=True, mask=NONE, colsum=False, res=False, res_alpha=0.1, res_pre=False,
+            x_act=NONE, pre_scale=1.0, flags=0, off=None, data="unit", deferred=False, part=None, act=NONE, host=False):
+    """Y [n][H][W][Cout] = [res + res_alpha *] (pre_scale conv3x3(x_act(X)) + bias [+ res]) * mask'(source), through
+    entry = 'plain' mvk_conv3x3, 'y' mvk_conv3x3_y, 'res' mvk_conv3x3_res, 'f' mvk_conv3x3_f, 's' mvk_conv3x3_s, 's2'
+    mvk_conv3x3_s2 (second output: the value before the residual sum), 's_part' mvk_conv3x3_s_part (part = (x_channels, x_off): X
+    and the pack have x_channels channels, the launch convolves the Cin channels from x_off).  The references are those of the
+    pre-activation; act != 0 is for the activation tests, which compare launches with each other.
+    off: 'x' | 'bias' | 'y' | 'mask' at storage offset 1.  data: 'unit', 'spread' (images and weight rows over e^(+-3 sigma)),
+    'loose' (operand bound 1000x above max |X|), 'tiny' (an image half and a weight row 2^-30 of the rest), 'chan' (input channels
+    over e^(+-1.5 sigma): the operands of the 2304-term sums)."""
+    import conv3_ref as R3
+
+    xc, xo = part if part is not None else (Cin, 0)
+    x, w, b, src, rs, cinit = R3.fwd_operands(seed, n, H, W, xc, Cout, spread=3.0 if data == "spread" else 0.0, tiny=data == "tiny",
+                                              chan=1.5 if data == "chan" else 0.0)
+    b = b if bias else None
+    if mask == SIGMOID:
+        src = torch.sigmoid(src)
+    scaled = entry in ("s", "s2", "s_part")
+    xb, wb = float(x.abs().max()) * (1000.0 if data == "loose" else 1.0), float(w.abs().max())
+    r = R3.conv3_fwd(x[:, xo:xo + Cin], w[:, xo:xo + Cin], b, x_act=x_act, pre_scale=pre_scale, mask_src=src if mask else None,
+                     mask_act=mask, res=rs if res else None, res_alpha=res_alpha, res_pre=res_pre, colsum=colsum,
+                     floor_bounds=(xb, wb) if scaled else None, want_h=host)
+    nhwc = lambda t: t.permute(0, 2, 3, 1)  # noqa: E731
+    outs = [_out3(r["y"], nhwc, shape=(n, H, W, Cout))]
+    if colsum:
+        outs.append(_out3(r["colsum"], init=cinit))
+    if entry == "s2":
+        outs.append(_out3(r["a"], nhwc, shape=(n, H, W, Cout)))
+    if host:
+        return Prep(None, outs, deferred=deferred, flags=flags)
+    from multivae_amd._lib import call, ptr, stream_ptr
+
+    d = dev()
+    al = lambda t, name: None if t is None else (unaligned(t.to(d)) if off == name else t.contiguous().to(d))  # noqa: E731
+    Xd, Wd, bd = al(_nhwc(x), "x"), R3.pack_fwd(w).to(d), al(b, "bias")
+    sd, rd = al(_nhwc(src) if mask else None, "mask"), (_nhwc(rs).to(d) if res else None)
+    yoff = unaligned(torch.full((n, H, W, Cout), float("nan"))) if off == "y" else None
+    xam, wam, yam = torch.full((1,), xb, device=d), torch.full((1,), wb, device=d), torch.zeros(1, device=d)
+    wsp, wsn = WS("ws")
+
+    def run(bufs):
+        Y = bufs[0] if yoff is None else yoff
+        cs = ptr(bufs[1]) if colsum else None
+        dims = (n, H, W, Cin, Cout)
+        if entry == "plain":
+            call("mvk_conv3x3", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, cs, wsp, wsn, stream_ptr())
+        elif entry == "y":
+            call("mvk_conv3x3_y", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, cs, ptr(yam), wsp, wsn, stream_ptr())
+        elif entry == "res":
+            call("mvk_conv3x3_res", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, ptr(rd), res_alpha, wsp, wsn,
+                 stream_ptr())
+        elif entry == "f":
+            call("mvk_conv3x3_f", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, ptr(rd), res_alpha, cs, x_act,
+                 pre_scale, wsp, wsn, stream_ptr())
+        elif entry == "s":
+            call("mvk_conv3x3_s", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, ptr(rd), res_alpha, cs, x_act,
+                 pre_scale, ptr(xam), ptr(wam), ptr(yam), wsp, wsn, stream_ptr())
+        elif entry == "s2":
+            call("mvk_conv3x3_s2", ptr(Xd), ptr(Wd), ptr(bd), ptr(Y), ptr(bufs[-1]), *dims, act, ptr(rd), res_alpha, ptr(xam),
+                 ptr(wam), ptr(yam), wsp, wsn, stream_ptr())
+        else:
+            call("mvk_conv3x3_s_part", ptr(Xd), xc, xo, ptr(Wd), ptr(bd), ptr(Y), *dims, act, ptr(sd), mask, ptr(rd), int(res_pre),
+                 x_act, pre_scale, ptr(xam), ptr(wam), ptr(yam), stream_ptr())
+        if yoff is not None:
+            bufs[0].copy_(yoff)
+
+    p = Prep(run, outs, deferred=deferred, flags=flags, keep=[Xd, Wd, bd, sd, rd, xam, wam, yam, yoff])
+    p.yam = yam
+    return p
+
+
+def p_conv3_wgrad(seed, n, H, W, Cin, Cout, entry="plain", x_act=NONE, dy_scale=1.0, db=False, ws="ws", det=True, deferred=False,
+                  flags=0, data="unit", host=False):
+    """dWref [Cout][Cin][3][3] += dy_scale * d/dW sum(conv3x3(x_act(X), W) dY), db [Cout] += dy_scale * sum dY, through entry =
+    'plain' mvk_conv3x3_wgrad, 'f' mvk_conv3x3_wgrad_f, 's' mvk_conv3x3_wgrad_s.  ws: 'ws' ample, 'none' NULL, 'unaligned' (storage
+    offset 1), or a number of floats."""
+    import conv3_ref as R3
+
+    x, dy, init, binit = R3.wgrad_operands(seed, n, H, W, Cin, Cout, spread=3.0 if data == "spread" else 0.0)
+    xb, yb = float(x.abs().max()), float(dy.abs().max())
+    r = R3.conv3_wgrad(x, dy, x_act=x_act, dy_scale=dy_scale, floor_bounds=(xb, yb) if entry == "s" else None, want_h=host)
+    outs = [_out3(r["dw"], init=init)]
+    if db:
+        outs.append(_out3(r["db"], init=binit))
+    if host:
+        return Prep(None, outs, det=det, deferred=deferred, flags=flags)
+    from multivae_amd._lib import call, ptr, stream_ptr
+
+    d = dev()
+    Xd, dYd = _nhwc(x).to(d), _nhwc(dy).to(d)
+    xam, yam = torch.full((1,), xb, device=d), torch.full((1,), yb, device=d)
+    if ws == "unaligned":
+        import ctypes
+
+        wsp, wsn = ctypes.c_void_p(_ws().data_ptr() + 4), _ws().numel() - 1
+    elif isinstance(ws, int):
+        wsp, wsn = WS("ws")[0], ws
+    else:
+        wsp, wsn = WS(ws)
+
+    def run(bufs):
+        dbp = ptr(bufs[1]) if db else None
+        if entry == "plain":
+            call("mvk_conv3x3_wgrad", ptr(Xd), ptr(dYd), ptr(bufs[0]), n, H, W, Cin, Cout, wsp, wsn, stream_ptr())
+        elif entry == "f":
+            call("mvk_conv3x3_wgrad_f", ptr(Xd), ptr(dYd), ptr(bufs[0]), dbp, n, H, W, Cin, Cout, x_act, dy_scale, wsp, wsn, stream_ptr())
+        else:
+            call("mvk_conv3x3_wgrad_s", ptr(Xd), ptr(dYd), ptr(bufs[0]), dbp, n, H, W, Cin, Cout, x_act, dy_scale, ptr(xam), ptr(yam),
+                 wsp, wsn, stream_ptr())
+
+    return Prep(run, outs, det=det, deferred=deferred, flags=flags, keep=[Xd, dYd, xam, yam])
+
+
 # ---- the dispatch table -------------------------------------------------------------------------------------------------
 @dataclass
 class Case:
@@ -706,7 +840,9 @@ class Case:
 
 
 def case(id_, fn, kw, expect, f32=None, note=""):
-    return Case(id_, lambda: fn(zlib.crc32(id_.encode()) % 100003, **kw), tuple(sorted(expect)), None if f32 is None else tuple(sorted(f32)), note)
+    c = Case(id_, lambda: fn(zlib.crc32(id_.encode()) % 100003, **kw), tuple(sorted(expect)), None if f32 is None else tuple(sorted(f32)), note)
+    c.fn, c.kw = fn, kw  # (tests/test_conv3_ref_host.py builds the host references of the 3x3 cases from them)
+    return c
 
 
 CASES = [
@@ -919,6 +1055,37 @@ CASES += [
          [bf(128, 64, "R", "N"), RED], [fast(64, 64, 32, "R", "N"), RED], "E_UNFLATREF, 16 tiles x 16 slices"),
     case("flatten-bf128x32-plainR-bmN-Econvref16", p_flatten, dict(n=512, Cu=64, Cv=20),
          [bf(128, 32, "R", "N"), RED], [fast(128, 32, 32, "R", "N"), RED], "E_CONVREF (16 taps)"),
+
+    # --- 3x3 / stride-1 convolutions on the tiled path (tw = 3, mul = 1 gather; the register-stationary kernels off: 0x400).
+    # The image-side kernels of conv3small.hip have no switch: these shapes are ones they decline.
+    case("c3fwd-bf128x32-row-bmN-small-grid", p_conv3, dict(n=3, H=7, W=7, Cin=32, Cout=32, flags=TILED_ONLY),
+         [bf(128, 32, "ROW", "N")], [fast(128, 32, 32, "ROW", "N")], "AM_ROW gather of a 3x3 window; N <= 32: 2 blocks"),
+    case("c3fwd-bf128x64-row-bmN-256blocks", p_conv3, dict(n=16, H=32, W=32, Cin=32, Cout=128, bias=False, flags=TILED_ONLY),
+         [bf(128, 64, "ROW", "N")], [fast(64, 64, 32, "ROW", "N")], "16384 positions x 2 column tiles = 256 blocks"),
+    case("c3bwdd-bf128x32-row-mask-colsum-fused", p_conv3,
+         dict(n=3, H=7, W=7, Cin=64, Cout=32, bias=False, mask=LEAKY, colsum=True, flags=TILED_ONLY),
+         [bf(128, 32, "ROW", "N"), FIN], [fast(128, 32, 32, "ROW", "N"), FIN], "backward-data form: epilogue mask + fused column sums"),
+    case("c3bwdd-bf128x64-row-mask-colsum-256blocks", p_conv3,
+         dict(n=16, H=32, W=32, Cin=32, Cout=128, bias=False, mask=RELU, colsum=True, flags=TILED_ONLY),
+         [bf(128, 64, "ROW", "N"), FIN], [fast(64, 64, 32, "ROW", "N"), FIN], "128 row tiles of partial column sums"),
+    case("c3fwd-generic-K27-Cout6", p_conv3, dict(n=2, H=5, W=5, Cin=3, Cout=6), [gen(128, 32)], None,
+         "Cout % 4 != 0: conv3_smallcin declines; Cin % 4 != 0: no vec4 -> generic, K = 27"),
+    case("c3fwd-generic-Cin6-Cout10", p_conv3, dict(n=1, H=5, W=9, Cin=6, Cout=10, mask=RELU), [gen(128, 32)], None, "Cin % 4 != 0"),
+    case("c3fwd-generic-N3-Cin24", p_conv3, dict(n=2, H=5, W=5, Cin=24, Cout=3), [gen(128, 32)], None,
+         "Cin % 16 != 0: conv3_smallcout declines; N = 3: the weight pack has no 16-byte rows -> generic"),
+    case("c3res-bf128x32-row-residual-mask", p_conv3,
+         dict(n=3, H=7, W=7, Cin=32, Cout=32, entry="res", res=True, mask=LEAKY, flags=TILED_ONLY),
+         [bf(128, 32, "ROW", "N")], [fast(128, 32, 32, "ROW", "N")], "mvk_conv3x3_res: res + alpha * (.) in the epilogue"),
+    case("c3fwd-bf128x32-row-K2304", p_conv3, dict(n=2, H=7, W=7, Cin=256, Cout=32, flags=TILED_ONLY),
+         [bf(128, 32, "ROW", "N")], [fast(128, 32, 32, "ROW", "N")],
+         "K = 2304 in one accumulator chain (no split K in the forward): 0.17x the bound on the split engine, 0.28x on the exact one"),
+    case("c3wgrad-bf128x64-col-splitk_ws-convref9", p_conv3_wgrad, dict(n=64, H=4, W=4, Cin=64, Cout=128, flags=TILED_ONLY),
+         [bf(128, 64, "COL", "N"), RED], [fast(64, 64, 32, "COL", "N"), RED],
+         "AM_COL, E_CONVREF with taps = 9; 10 tiles x 32 slices of 2 k-tiles (target 768) = 320 blocks"),
+    case("c3wgrad-deferred", p_conv3_wgrad, dict(n=64, H=4, W=4, Cin=64, Cout=128, deferred=True, flags=TILED_ONLY),
+         [bf(128, 64, "COL", "N"), BATCH], [fast(64, 64, 32, "COL", "N"), BATCH], "deferred slabs"),
+    case("c3wgrad-noscratch-atomic", p_conv3_wgrad, dict(n=64, H=4, W=4, Cin=64, Cout=128, ws="none", det=False, flags=TILED_ONLY),
+         [bf(128, 64, "COL", "N")], [fast(64, 64, 32, "COL", "N")], "fp32-atomic split K"),
 ]
 
 
@@ -1036,7 +1203,8 @@ def check_case(c, engine_f32=F32_ENGINE, collect=False):
 
 @pytest.mark.parametrize("c", CASES, ids=[c.id for c in CASES])
 def test_dispatch_leaf(c):
-    check_case(c)
+    report = check_case(c)
+    print(c.id, {k: v for k, v in report.items() if k != "kernels"})
 
 
 def test_wgrad_pair_matches_two_launches():

@@ -1032,34 +1032,37 @@ def test_jmvae_posterior(K, M, B, L, Kk):
                                           # few positions, long reductions: the split-K route of the tiled engine (round 5)
                                           (32, 7, 7, 128, 128), (8, 7, 7, 256, 128), (32, 7, 7, 128, 256)])
 def test_conv3x3_fwd_bwd(K, n, H, W, Cin, Cout):
-    """mvk_conv3x3 / mvk_conv3x3_wgrad (+ kind-2 weight pack) vs F.conv2d(3, 1, 1) + LeakyReLU(0.2): forward, backward
-    data with the fused activation derivative and bias-gradient column sums, backward weight in the reference layout."""
+    """mvk_conv3x3 / mvk_conv3x3_wgrad (+ kind-2 weight pack) vs a float64 F.conv2d(3, 1, 1) + LeakyReLU(0.2): forward, backward
+    data with the fused activation derivative and bias-gradient column sums, backward weight in the reference layout.  The
+    backward references start from the pre-activation gradient the launches are fed (dy x the derivative at the kernel's own
+    output), in float64."""
     gen = g(31)
     x = torch.randn(n, Cin, H, W, generator=gen)
-    w = (torch.randn(Cout, Cin, 3, 3, generator=gen) / (3 * Cin ** 0.5)).requires_grad_(True)
-    b = (0.1 * torch.randn(Cout, generator=gen)).requires_grad_(True)
-    xin = F.leaky_relu(x, 0.2).requires_grad_(True)  # x itself is a LeakyReLU output: its derivative multiplies dx
-    y = F.leaky_relu(F.conv2d(xin, w, b, 1, 1), 0.2)
+    w = torch.randn(Cout, Cin, 3, 3, generator=gen) / (3 * Cin ** 0.5)
+    b = 0.1 * torch.randn(Cout, generator=gen)
+    xin = F.leaky_relu(x, 0.2)  # x itself is a LeakyReLU output: its derivative multiplies dx
+    y = F.leaky_relu(F.conv2d(xin.double(), w.double(), b.double(), 1, 1), 0.2)
     dy = torch.randn(n, Cout, H, W, generator=gen)
-    y.backward(dy)
-    dxin_pre = xin.grad * torch.where(xin > 0, 1.0, 0.2)  # gradient w.r.t. the pre-activation of xin
     d = dev()
     nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().to(d)
-    wd = w.detach().to(d)
+    wd = w.to(d)
     (wf, wb), = K.pack_weights([(wd, "c3", True, True)])
     X = nhwc(xin)
-    Y = K.conv3x3(X, wf, b.detach().to(d), n, H, W, Cin, Cout, act=K.LEAKY)
-    close(Y, nhwc(y), what="conv3x3 forward")
+    Y = K.conv3x3(X, wf, b.to(d), n, H, W, Cin, Cout, act=K.LEAKY)
+    close(Y, nhwc(y), what="conv3x3 forward", rtol=3e-6)
     dpre = nhwc(dy) * torch.where(Y > 0, 1.0, 0.2)
+    dpre64 = dpre.cpu().permute(0, 3, 1, 2).double()
+    dxin_pre = F.conv_transpose2d(dpre64, w.double(), None, 1, 1) * torch.where(xin > 0, 1.0, 0.2).double()
     bparam = torch.zeros(Cin, device=d).requires_grad_(True)  # stands for the bias of the layer that produced xin
     bparam.grad = torch.zeros(Cin, device=d)
     dX, _ = K.conv3x3(dpre, wb, None, n, H, W, Cout, Cin, y_act_src=X, y_src_act=K.LEAKY, out_bias=bparam)
-    close(dX, nhwc(dxin_pre), what="conv3x3 backward data")
-    close(bparam.grad, dxin_pre.sum((0, 2, 3)), what="fused bias-gradient column sums")
+    close(dX, nhwc(dxin_pre), what="conv3x3 backward data", rtol=3e-6)
+    close(bparam.grad, dxin_pre.sum((0, 2, 3)), what="fused bias-gradient column sums", rtol=1e-5)
     wparam = wd.clone().requires_grad_(True)
     wparam.grad = torch.zeros_like(wparam)
     K.conv3x3_wgrad(X, dpre, wparam, n, H, W, Cin, Cout)
-    close(wparam.grad, w.grad, what="conv3x3 backward weight")
+    close(wparam.grad, torch.nn.grad.conv2d_weight(xin.double(), w.shape, dpre64, stride=1, padding=1), what="conv3x3 backward weight",
+          rtol=3e-6)
 
 
 @pytest.mark.parametrize("n,H,W,Cin,Cout", [(3, 64, 64, 3, 64), (7, 28, 28, 3, 64), (2, 9, 13, 1, 32), (5, 28, 28, 4, 128)])
@@ -1428,11 +1431,12 @@ def test_conv3x3_residual_epilogue(K, n, H, W, Cin, Cout):
     src = torch.randn(n, Cout, H, W, generator=gen)
     nhwc = lambda t: t.detach().permute(0, 2, 3, 1).contiguous().to(d)
     (wf, _), = K.pack_weights([(w.to(d), "c3", True, True)])
-    conv = F.conv2d(x, w, b, 1, 1)
+    conv = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
     Y = K.conv3x3(nhwc(x), wf, b.to(d), n, H, W, Cin, Cout, act=K.NONE, res=nhwc(res), res_alpha=0.1)
-    close(Y, nhwc(res + 0.1 * conv), what="res + 0.1 * conv")
+    close(Y, nhwc(res.double() + 0.1 * conv), what="res + 0.1 * conv", rtol=3e-6)
     Y = K.conv3x3(nhwc(x), wf, b.to(d), n, H, W, Cin, Cout, act=K.LEAKY, y_act_src=nhwc(src), y_src_act=K.LEAKY, res=nhwc(res))
-    close(Y, nhwc(res + F.leaky_relu(conv, 0.2) * torch.where(src > 0, 1.0, 0.2)), what="res + act(conv) * mask")
+    close(Y, nhwc(res.double() + F.leaky_relu(conv, 0.2) * torch.where(src > 0, 1.0, 0.2).double()), what="res + act(conv) * mask",
+          rtol=3e-6)
     with pytest.raises(Exception):
         K.conv3x3(nhwc(x), wf, None, n, H, W, Cin, Cout, res=nhwc(res), out_bias=torch.zeros(Cout, device=d))
 
