@@ -1027,6 +1027,7 @@ int mvk_conv4s2_scaled_ok(int n, int h, int w, int Cu, int Cv) {
 int mvk_conv4s2_down_s(const float* U, const float* Wdown, const float* bias, float* V, int n, int h, int w, int Cu, int Cv,
                        int act, const float* v_act_src, int v_act, float* colsum_acc, const float* x_amax, const float* w_amax,
                        float* y_amax, float* ws, int64_t ws_floats, const void* wfrag, void* stream) {
+  if (n == 0) return MVK_OK;  // empty batch, as mvk_conv4s2_down
   if (!mvk_conv4s2_scaled_ok(n, h, w, Cu, Cv) || (!x_amax && !y_amax)) return MVK_EINVAL;
   return conv4s2_down_impl(U, Wdown, bias, V, n, h, w, Cu, Cv, act, 0, nullptr, MVK_ACT_NONE, v_act_src, v_act, colsum_acc, ws,
                            ws_floats, 0, wfrag, x_amax, w_amax, y_amax, stream);
@@ -1099,6 +1100,7 @@ int mvk_conv4s2_up(const float* V, const float* Wup, const float* bias, float* U
 int mvk_conv4s2_up_s(const float* V, const float* Wup, const float* bias, float* U, int n, int h, int w, int Cu, int Cv, int act,
                      const float* u_act_src, int u_act, float* colsum_acc, const float* x_amax, const float* w_amax,
                      float* y_amax, float* ws, int64_t ws_floats, const void* wfrag, void* stream) {
+  if (n == 0) return MVK_OK;  // empty batch, as mvk_conv4s2_up
   if (!mvk_conv4s2_scaled_ok(n, h, w, Cu, Cv) || (!x_amax && !y_amax)) return MVK_EINVAL;
   return conv4s2_up_impl(V, Wup, bias, U, n, h, w, Cu, Cv, act, 0, u_act_src, u_act, colsum_acc, ws, ws_floats, 0, wfrag, x_amax,
                          w_amax, y_amax, stream);
@@ -1396,6 +1398,7 @@ static GemmDesc conv4s2_wgrad_desc(const float* U, const float* V, float* dWref,
 static int conv4s2_wgrad_impl(const float* U, const float* V, float* dWref, int n, int h, int w, int Cu, int Cv,
                               int u_nchw, const float* u_act_src, int u_act, float* ws, int64_t ws_floats,
                               const float* u_amax, const float* v_amax, void* stream) {
+  if (n == 0) return MVK_OK;  // empty batch: nothing to add (the split-K slice count below divides by the k-tiles)
   if (!U || !V || !dWref || n < 0 || h <= 0 || w <= 0 || Cu <= 0 || Cv <= 0 || (!u_amax != !v_amax)) return MVK_EINVAL;
   if (u_nchw && !u_act_src && smallcin_supported(Cu, Cv)) {
     const int rc = smallcin_wgrad(U, V, dWref, n, h, w, Cu, Cv, ws, ws_floats, mvk_stream(stream));
@@ -1492,6 +1495,7 @@ int mvk_conv4s2_wgrad_scaled_ok(int n, int h, int w, int Cu, int Cv) {
 }
 int mvk_conv4s2_wgrad_s(const float* U, const float* V, float* dWref, int n, int h, int w, int Cu, int Cv, const float* u_amax,
                         const float* v_amax, float* ws, int64_t ws_floats, void* stream) {
+  if (n == 0) return MVK_OK;  // empty batch, as mvk_conv4s2_wgrad
   if (!u_amax || !v_amax || !ws || !mvk_conv4s2_wgrad_scaled_ok(n, h, w, Cu, Cv)) return MVK_EINVAL;
   return conv4s2_wgrad_impl(U, V, dWref, n, h, w, Cu, Cv, 0, nullptr, MVK_ACT_NONE, ws, ws_floats, u_amax, v_amax, stream);
 }
