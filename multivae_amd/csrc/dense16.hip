@@ -176,17 +176,22 @@ __global__ __launch_bounds__(256) void d16_first_kernel(const D16First g) {
   const float s = mvk::f16_scale_of(bound);
   if (active)
     for (int r = rg; r < R && m0 + r < g.M; r += rgn) {
-      f32x4 acc = b4;
+      // K > 20: two fma chains (even / odd k-quads) of at most 16 products.  ONE chain of 32 + bias left 5e-7 sum |z w| in 1 of
+      // 5 M entries at K = 32 (tests/test_gpu_dense16.py first-m5130-n1024-k32: 1.08 x), the two stay at 0.74 of it.  Up to
+      // K = 20 (the workload's latent dimension) the one chain of <= 21 terms stays as it was, and with it every bit of h.
+      constexpr bool SPLIT = K4 > 5;
+      f32x4 acc = b4, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int q = 0; q < K4; ++q) {
         const f32x4 x = *reinterpret_cast<const f32x4*>(&xs[r][4 * q]);
+        f32x4& a = (SPLIT && (q & 1)) ? acc1 : acc;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[j] = fmaf(x[e], w[4 * q + e][j], acc[j]);
+          for (int j = 0; j < 4; ++j) a[j] = fmaf(x[e], w[4 * q + e][j], a[j]);
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = mvk_act(acc[j], g.act);
+      for (int j = 0; j < 4; ++j) acc[j] = mvk_act(SPLIT ? acc[j] + acc1[j] : acc[j], g.act);
       unsigned h0, l0, h1, l1_;
       mvk::f16_split(acc[0] * s, acc[1] * s, h0, l0);
       mvk::f16_split(acc[2] * s, acc[3] * s, h1, l1_);
