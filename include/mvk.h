@@ -303,6 +303,58 @@ int mvk_mmvaeplus_cross_latent_bwd(const float* dzc, const float* noise, int64_t
                                    float* dz, float* dprior_std, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CMVAE (models/cmvae/cmvae_model.py): MMVAE+ with a learnable mixture over C clusters as the prior of the shared latent.
+ * The reference's explicit expectation over q(c|u) = softmax_c(a_c) + 1e-20, a_c = log pi_c + log p(u|c) (:292-337), is
+ * evaluated in closed form: sum_c q_c (a_c - log q_c) = logsumexp_c a_c.
+ * ------------------------------------------------------------------------------------------------ */
+
+/* The cluster table (means, stds, log pi) of a launch is staged in LDS: 1 <= C <= MVK_CMVAE_MAX_CLUSTERS and
+ * C * (2 * (Ls | 1) + 1) + 4 * Ls <= MVK_CMVAE_MAX_LDS_FLOATS (the 4 * Ls: mvk_cmvae_latent_fwd only), MVK_EINVAL beyond.
+ * C = 64 fits up to Ls = 91, C = 128 up to Ls = 45, C = 10 up to Ls = 511.
+ * At least one entry of cluster_logits must be finite: with every logit at -inf the softmax is 0 / 0 and lpz, resp and pc_z are
+ * NaN, as torch.softmax of the same logits is (CMVAE.prune_clusters stops at two clusters and never gets there). */
+#define MVK_CMVAE_MAX_CLUSTERS 128
+#define MVK_CMVAE_MAX_LDS_FLOATS 12288
+
+/* The latent stage of mvk_mmvae_latent_fwd for the MMVAE+ layout [u (shared_dims = Ls < D), w (D - Ls)], ONE launch, same
+ * arguments, conventions (B == 0, M * K * B < 2^31, masks) and outputs z, lqz, lq_all, lqw, with the prior replaced by
+ *   lpz[c][k,b] = logsumexp_j(log_softmax(cluster_logits)_j + sum_{l < Ls} log p(u_l; cluster_mean[j,l], cluster_std[j,l]))
+ *                 + sum_{l >= Ls} log p(w_l; 0, wprior_std[l - Ls])
+ * and resp[c][k,b,j] = the softmax over j of the same terms (no 1e-20), which the backward launch reads.  cluster_mean,
+ * cluster_std: device [C, Ls]; cluster_logits: device [C] (log pi is computed in the launch; a logit of -inf makes the
+ * cluster absent: zero responsibility, no NaN, where the reference's literal form gives -inf through 1e-20 * -inf);
+ * wprior_std: device [D - Ls]; resp: HOST array of M device pointers [K,B,C]; lqw is required. */
+int mvk_cmvae_latent_fwd(const float* const* mu, const float* const* std, const float* const* noise,
+                         const uint8_t* const* masks, const float* cluster_mean, const float* cluster_std,
+                         const float* cluster_logits, const float* wprior_std, int M, int K, int B, int D, int family,
+                         int C, float* const* z, float* const* lpz, float* const* lqz, float* const* lq_all,
+                         int shared_dims, float* const* lqw, float* const* resp, void* stream);
+
+/* Latent-side backward, ONE launch with the per-b ownership of mvk_mmvae_latent_bwd (dmu, dstd [B,D] summed over c and k in a
+ * fixed order, no atomics).  The prior's pull on u is coef * beta * sum_j resp_j * d log p(u; mean_j, std_j) / du.
+ * dparams [B, C * Ls + C] (overwritten): row b holds the terms of batch row b of d loss / d cluster_mean ([C, Ls], entry
+ * (j, l) = coef * beta * resp_j * d log p / d mean_jl) followed by d loss / d cluster_logits ([C], entry i = coef * beta *
+ * (resp_i - pi_i)); the caller sums the rows with one mvk_colsum_acc.  coef = d loss / d lw = -gscale * w / n_avail, IWAE and
+ * DReG alike: under DReG only the path through the reparameterised sample takes w a second time (as dprior_std in
+ * mvk_mmvae_latent_bwd).  The cluster stds and wprior_std get no gradient (the reference fixes them). */
+int mvk_cmvae_latent_bwd(const float* const* mu, const float* const* std, const float* const* noise,
+                         const float* const* z, const uint8_t* const* masks, const float* cluster_mean,
+                         const float* cluster_std, const float* cluster_logits, const float* wprior_std,
+                         const float* const* w, const float* const* lq_all, const float* const* lqz,
+                         const float* const* resp, const float* const* dz_dec, int M, int K, int B, int D, int family,
+                         int dreg, int C, const float* gscale, float* const* dmu, float* const* dstd, float* dparams,
+                         int shared_dims, float beta, void* stream);
+
+/* predict_clusters (:546-619) for R rows z [R, Ls], ONE launch: pc_z [C, R] = softmax_j(log(softmax(cluster_logits)_j + 1e-20)
+ * + sum_l log p(z_l; cluster_mean[j,l], cluster_std[j,l])) (here the reference does add 1e-20 inside the log: a pruned cluster
+ * has log 1e-20, not -inf), argmax [R] (int64) = the first maximum of pc_z[:, r], norm_llik [R] (nullable) =
+ * sum_j pc_j (lpz_j + lpc_j - log pc_j) / Ls, evaluated as logsumexp_j(lpc_j + lpz_j) / Ls (finite where pc_j underflows to 0
+ * and the literal form is 0 * inf).  R == 0 returns MVK_OK without a launch; R < 2^31. */
+int mvk_cmvae_assign(const float* z, const float* cluster_mean, const float* cluster_std, const float* cluster_logits,
+                     int64_t R, int Ls, int family, int C, float* pc_z, int64_t* argmax, float* norm_llik,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Importance-sampled joint likelihood (compute_joint_nll; metrics/likelihoods/likelihoods.py:39-56 is the caller)
  * ------------------------------------------------------------------------------------------------ */
 

@@ -43,6 +43,8 @@ DIST = {"normal": 0, "laplace": 1, "bernoulli": 2, "categorical": 3}
 ACT = {None: 0, "none": 0, "relu": 1, "sigmoid": 2, "leaky_relu_0.2": 3}
 FAMILY = {"normal": 0, "laplace_with_softmax": 1, "normal_with_softplus": 2}  # 2: std kernels only (density = normal)
 MAX_MODALITIES = 8
+CMVAE_MAX_CLUSTERS = 128  # MVK_CMVAE_MAX_CLUSTERS
+CMVAE_MAX_LDS_FLOATS = 12288  # MVK_CMVAE_MAX_LDS_FLOATS
 
 _p = C.c_void_p
 _i = C.c_int
@@ -169,6 +171,10 @@ PROTOTYPES = {
     "mvk_mmvae_latent_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _f, _p],
     "mvk_mmvaeplus_cross_latent_fwd": [_p, _p, _p, _i64, _i, _i, _i, _p, _p],
     "mvk_mmvaeplus_cross_latent_bwd": [_p, _p, _i64, _i, _i, _i, _p, _p, _p],
+    "mvk_cmvae_latent_fwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p],
+    "mvk_cmvae_latent_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p,
+                             _i, _f, _p],
+    "mvk_cmvae_assign": [_p, _p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p],
     "mvk_mvae_posterior_fwd": [_p, _p, _p, _i, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p],
     "mvk_mvae_posterior_bwd": [_p, _p, _p, _i, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p],
     "mvk_gauss_sample_kl_fwd": [_p, _p, _p, _i, _i, _i, _p, _p, _p],

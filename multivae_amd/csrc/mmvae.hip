@@ -7,11 +7,11 @@
 // cross-modal decoder input is sampled from the target modality's prior (cross_latent kernels).  All tensors are small ([K,B,L], L ~ 20-64): these kernels are
 // latency-bound; the design goal is few launches and deterministic reductions.
 #include "common.hpp"
+#include "latent.hpp"  // lat_logp, lat_dlogp_dz, lat_dlogp_dsd, lat_t
 
 namespace {
 
 constexpr int MAXM = MVK_MAX_MODALITIES;
-constexpr float HALF_LOG_2PI = 0.918938533204672742f;
 
 struct MmPtrs {
   const float* mu[MAXM];
@@ -24,31 +24,6 @@ struct MmPtrs {
   float* lq_all[MAXM];
   float* lqw[MAXM];  // MMVAE+: log q_c(w_c) rows (NULL for MMVAE)
 };
-
-__device__ __forceinline__ float lat_logp(int family, float z, float loc, float sd) {
-  if (family == MVK_FAMILY_NORMAL) {
-    const float d = z - loc;
-    return -(d * d) / (2.0f * sd * sd) - logf(sd) - HALF_LOG_2PI;
-  }
-  return -logf(2.0f * sd) - fabsf(z - loc) / sd;
-}
-// d logp / d z  (d/d loc is its negative)
-__device__ __forceinline__ float lat_dlogp_dz(int family, float z, float loc, float sd) {
-  const float d = z - loc;
-  if (family == MVK_FAMILY_NORMAL) return -d / (sd * sd);
-  return -(d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) / sd;
-}
-__device__ __forceinline__ float lat_dlogp_dsd(int family, float z, float loc, float sd) {
-  const float d = z - loc;
-  if (family == MVK_FAMILY_NORMAL) return d * d / (sd * sd * sd) - 1.0f / sd;
-  return -1.0f / sd + fabsf(d) / (sd * sd);
-}
-// z = loc + sd * t(noise)
-__device__ __forceinline__ float lat_t(int family, float noise) {
-  if (family == MVK_FAMILY_NORMAL) return noise;
-  const float sg = noise > 0.f ? 1.f : (noise < 0.f ? -1.f : 0.f);
-  return -sg * log1pf(-fabsf(noise));
-}
 
 // ---- std from log-variance ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void std_fwd_kernel(const float* __restrict__ lv, int rows, int L, int family,

@@ -2293,6 +2293,7 @@ class MMVAEState:
         self.lqw = None          # MMVAE+: log q_c(w_c) rows
         self.shared_dims = None  # MMVAE+: leading latent dims that enter the mixture (None = all)
         self.beta = 1.0          # MMVAE+: weight of the latent terms of lw
+        self.resp = None         # CMVAE: q(cluster | u_c) rows [K,B,C]
 
 
 class MMVAELatentFn(Function):
@@ -2440,6 +2441,82 @@ class MMVAEObjectiveFn(Function):
                 call("mvk_scale_by_device_scalar", ptr(g), g.numel(), ptr(st.gloss), stream_ptr())
             grads += gs
         return (None, None, None, None, *grads)
+
+
+# =====================================================================================================
+# CMVAE: the MMVAE+ latent stage with a mixture over clusters as the prior of the shared latent
+# =====================================================================================================
+class CMVAELatentFn(Function):
+    """(mu_c, std_c)_c, cluster means [C,Ls] and logits [C] -> z_c [K,B,D] for every conditioning modality; fills the
+    MMVAEState (lpz with the mixture prior, lqz, lq_all, lqw) for MMVAEObjectiveFn and keeps the responsibilities for the
+    backward launch.  Gradients: cluster means, logits, mu_c, std_c; none for the cluster stds and the private prior std
+    (cmvae_model.py:100-105, :123-128 fix them)."""
+
+    @staticmethod
+    def forward(ctx, state, noises, masks, family, dreg, wprior_std, cluster_stds, cluster_means, cluster_logits, *mus_stds):
+        M = len(mus_stds) // 2
+        mus = [_c(t) for t in mus_stds[:M]]
+        sds = [_c(t) for t in mus_stds[M:]]
+        cmean, csd, clogit = _c(cluster_means), _c(cluster_stds), _c(cluster_logits.reshape(-1))
+        wsd = _c(wprior_std.reshape(-1))
+        K, B, D = noises[0].shape
+        C, Ls = cmean.shape
+        assert Ls == int(state.shared_dims) and wsd.numel() == D - Ls and csd.shape == cmean.shape and clogit.numel() == C
+        zs = [_new((K, B, D), mus[0]) for _ in range(M)]
+        state.lpz = [_new((K, B), mus[0]) for _ in range(M)]
+        state.lqz = [_new((K, B), mus[0]) for _ in range(M)]
+        state.lq_all = [_new((M, K, B), mus[0]) for _ in range(M)]
+        state.lqw = [_new((K, B), mus[0]) for _ in range(M)]
+        state.resp = [_new((K, B, C), mus[0]) for _ in range(M)]
+        marr = ptr_array(masks) if masks is not None else None
+        call("mvk_cmvae_latent_fwd", ptr_array(mus), ptr_array(sds), ptr_array(noises), marr, ptr(cmean), ptr(csd), ptr(clogit),
+             ptr(wsd), M, K, B, D, family, C, ptr_array(zs), ptr_array(state.lpz), ptr_array(state.lqz),
+             ptr_array(state.lq_all), Ls, ptr_array(state.lqw), ptr_array(state.resp), stream_ptr())
+        state.z = zs
+        ctx.save_for_backward(cmean, csd, clogit, wsd, *mus, *sds)
+        ctx.state, ctx.noises, ctx.masks = state, noises, masks
+        ctx.family, ctx.dreg, ctx.M = family, dreg, M
+        ctx.logit_shape = cluster_logits.shape
+        return tuple(zs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *dzs):
+        saved = ctx.saved_tensors
+        cmean, csd, clogit, wsd = saved[:4]
+        M = ctx.M
+        mus, sds = saved[4 : 4 + M], saved[4 + M :]
+        st = ctx.state
+        K, B, D = ctx.noises[0].shape
+        C, Ls = cmean.shape
+        dzs = [(_c(d) if d is not None else torch.zeros_like(st.z[i])) for i, d in enumerate(dzs)]
+        dmus = [_new((B, D), mus[0]) for _ in range(M)]
+        dsds = [_new((B, D), mus[0]) for _ in range(M)]
+        n = C * Ls + C
+        rows = _new((B, n), mus[0])  # per-row terms of d loss / d (means, logits), summed below in a fixed order
+        marr = ptr_array(ctx.masks) if ctx.masks is not None else None
+        call("mvk_cmvae_latent_bwd", ptr_array(mus), ptr_array(sds), ptr_array(ctx.noises), ptr_array(st.z), marr, ptr(cmean),
+             ptr(csd), ptr(clogit), ptr(wsd), ptr_array(st.w), ptr_array(st.lq_all), ptr_array(st.lqz), ptr_array(st.resp),
+             ptr_array(dzs), M, K, B, D, ctx.family, ctx.dreg, C, ptr(st.gloss), ptr_array(dmus), ptr_array(dsds), ptr(rows),
+             Ls, float(st.beta), stream_ptr())
+        dparams = _zeros((n,), mus[0])
+        ws = _ws(rows)
+        call("mvk_colsum_acc", ptr(rows), None, NONE, ptr(dparams), B, n, ptr(ws), ws.numel(), stream_ptr())
+        return (None, None, None, None, None, None, None, dparams[: C * Ls].view(C, Ls), dparams[C * Ls :].view(ctx.logit_shape),
+                *dmus, *dsds)
+
+
+def cmvae_assign(z, cluster_means, cluster_stds, cluster_logits, family, want_lliks=False):
+    """Rows z [R,Ls] -> pc_z [C,R], argmax [R] (int64, first maximum), norm_llik [R] or None (mvk_cmvae_assign)."""
+    z, cmean, csd, clogit = _c(z), _c(cluster_means), _c(cluster_stds), _c(cluster_logits.reshape(-1))
+    R, Ls = z.shape
+    C = cmean.shape[0]
+    pc = _new((C, R), z)
+    amax = torch.empty(R, dtype=torch.int64, device=z.device)
+    nll = _new((R,), z) if want_lliks else None
+    call("mvk_cmvae_assign", ptr(z), ptr(cmean), ptr(csd), ptr(clogit), R, Ls, family, C, ptr(pc), ptr(amax), ptr(nll),
+         stream_ptr())
+    return pc, amax, nll
 
 
 # =====================================================================================================

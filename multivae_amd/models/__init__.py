@@ -10,7 +10,8 @@ from .crmvae import CRMVAE, CRMVAEConfig
 from .dmvae import DMVAE, DMVAEConfig
 from .nexus import Nexus, NexusConfig
 from .cvae import CVAE, CVAEConfig
+from .cmvae import CMVAE, CMVAEConfig
 from .auto_model import AutoConfig, AutoModel  # noqa: E402  (needs the model classes above)
 
 __all__ = ["BaseAEConfig", "BaseMultiVAE", "BaseMultiVAEConfig", "ModelOutput", "MMVAE", "MMVAEConfig", "MoPoE",
-           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig", "CVAE", "CVAEConfig"]
+           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig", "CVAE", "CVAEConfig", "CMVAE", "CMVAEConfig"]

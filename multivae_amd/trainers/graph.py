@@ -37,7 +37,16 @@ from ..data.datasets.base import DatasetOutput
 class GraphedStep:
     def __init__(self, model, flat, inputs, noise=None, warmup=3, capture_error_mode="global", optimizer=None, overlap=False,
                  rotate=None, **fwd_kwargs):
-        """optimizer: a FusedAdam(zero_grad_in_step=True) to capture behind the backward pass (single-GPU steps; `includes_optimizer`
+        """Build it BEFORE the first eager backward pass of `model`, or after every output of such a pass has been released (as
+        BaseTrainer does: it keeps no output across steps).  Parameters whose gradients arrive through autograd's own accumulation
+        (MMVAE+'s prior log-variances, CMVAE's cluster means and logits: anything not written straight into the flat gradient
+        buffer by a kernel) keep their accumulation node, and the stream it was made on, for as long as an earlier output holds
+        the autograd graph; a capture on another stream that reaches such a node ended, in the one case seen, with a segmentation
+        fault inside the HIP runtime at the end of the capture: the process dies, no Python exception is raised, and the
+        trainer's fallback to eager steps cannot catch it.  torch announces the condition with its "AccumulateGrad node's stream
+        does not match" warning.
+
+        optimizer: a FusedAdam(zero_grad_in_step=True) to capture behind the backward pass (single-GPU steps; `includes_optimizer`
         says whether it was).  overlap: record the point where the early part of the gradient buffer is final (data-parallel
         steps; `reduce_and_step` uses it).  rotate: the FusedAdam the caller steps behind every replay — the decoders' late
         leaves and their part of the update move to the head of the next replay (`rotated` says whether the model had any)."""
@@ -109,9 +118,17 @@ class GraphedStep:
     def _clone(noise):
         if noise is None:
             return None
-        if isinstance(noise, dict):
-            return {k: v.detach().clone() for k, v in noise.items()}
+        if isinstance(noise, dict):  # MMVAE+ / CMVAE: one dict of draws per conditioning modality
+            return {k: GraphedStep._clone(v) for k, v in noise.items()}
         return noise.detach().clone()
+
+    @staticmethod
+    def _copy_noise(dst, src):
+        if isinstance(src, dict):
+            for k, v in src.items():
+                GraphedStep._copy_noise(dst[k], v)
+        elif src is not dst:
+            dst.copy_(src, non_blocking=True)
 
     def _body(self, capture=False):
         kw = dict(self.fwd_kwargs)
@@ -151,11 +168,7 @@ class GraphedStep:
                 pairs += [(self.masks[m], v) for m, v in inputs.masks.items() if v is not self.masks[m]]
             self._copy_in(pairs)
         if noise is not None and self.noise is not None:
-            if isinstance(noise, dict):
-                for k, v in noise.items():
-                    self.noise[k].copy_(v, non_blocking=True)
-            elif noise is not self.noise:
-                self.noise.copy_(noise, non_blocking=True)
+            self._copy_noise(self.noise, noise)
         if self.optimizer is not None:
             self.optimizer.sync_device_state()  # a copy only when lr / step changed behind the graph's back
         self.flat.zero_grad()  # free after FusedAdam(zero_grad_in_step=True).step()
