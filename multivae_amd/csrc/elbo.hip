@@ -437,24 +437,6 @@ __device__ __forceinline__ void recon_vec_body(const mvk_recon_desc& d, int B, i
   }
 }
 
-// Sample chunks per batch row: one block walks up to KC samples of its row (x is read once).  MVK_RECON_CHUNK caps the
-// chunk length (experiment hook).  Measured in the MoPoE step (MnistSvhn, K=10, B=512): 10 samples per block 28.5 us,
-// 5: 30.3, 3: 34.0, 2: 31.8 -- the coarsest cut wins.
-static int recon_max_chunk() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = mvk_tune("MVK_RECON_CHUNK");
-    v = e ? atoi(e) : KC;
-    if (v < 1) v = 1;
-    if (v > KC) v = KC;
-  }
-  return v;
-}
-static int recon_kchunks(int K, long long D) {
-  const int cap = D > 1024 ? recon_max_chunk() : KC;
-  return (K + cap - 1) / cap;
-}
-
 // MODE 0: scalar path (unaligned rows / row length not a multiple of 4); 1: vector path, Normal / Laplace rows; 2: vector
 // path, Bernoulli rows (a separate instantiation: its exp / log1p temporaries cost 24 more registers, i.e. 2 waves per
 // SIMD that the streaming Normal / Laplace rows would lose)
@@ -605,7 +587,9 @@ static int launch_recon(const mvk_recon_desc* descs, int n_mod, int K, int B, bo
       if (group != pass) continue;
       tb.d[tb.n] = d;
       tb.block_start[tb.n] = blocks;
-      tb.kchunks[tb.n] = recon_kchunks(K, d.D);
+      // sample chunks per batch row: one block walks up to KC samples of its row (x is read once).  Measured in the MoPoE step
+      // (MnistSvhn, K=10, B=512): 10 samples per block 28.5 us, 5: 30.3, 3: 34.0, 2: 31.8 -- the coarsest cut wins.
+      tb.kchunks[tb.n] = (K + KC - 1) / KC;
       blocks += B * tb.kchunks[tb.n];
       tb.n++;
     }

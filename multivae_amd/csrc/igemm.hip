@@ -224,14 +224,8 @@ static int launch_bf_tile(const GemmDesc& d, int zdim, hipStream_t s, int amode,
   return 1;
 }
 
-static int bf_min_blocks() {  // smallest grid that still goes to the split engine (MVK_BF_MIN_BLOCKS overrides)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = mvk_tune("MVK_BF_MIN_BLOCKS");
-    v = e ? atoi(e) : 256;  // measured on the MnistSvhn step: 160-256 best, 384 and < 100 1-2 % slower
-  }
-  return v;
-}
+// smallest grid that still goes to the split engine (measured on the MnistSvhn step: 160-256 best, 384 and < 100 1-2 % slower)
+constexpr int BF_MIN_BLOCKS = 256;
 
 static int g_engine = -1;  // 1 = split-bf16 MFMA (default), 0 = fp32 MFMA (MVK_ENGINE=f32)
 static int engine() {
@@ -290,7 +284,7 @@ static int try_launch_fast(const GemmDesc& d, int zdim, hipStream_t s) {
       rc = launch_bf_tile<128, 32>(d, zdim, s, amode, bmode, aact);
     } else if (d.N > 64 && amode == AM_COL && nb(128, 128) >= 384) {
       rc = launch_bf_tile<128, 128>(d, zdim, s, amode, bmode, aact);
-    } else if (nb(128, 64) >= bf_min_blocks() || amode == AM_ROW3) {
+    } else if (nb(128, 64) >= BF_MIN_BLOCKS || amode == AM_ROW3) {
       rc = launch_bf_tile<128, 64>(d, zdim, s, amode, bmode, aact);
     }
     if (rc != 1) return rc;
@@ -343,31 +337,20 @@ int launch_igemm(const GemmDesc& d_in, int zdim, hipStream_t s, LaunchInfo* info
   return launch_cfg<64, 64>(d, zdim, s);
 }
 
-// experiment hook: MVK_SPLITK_TARGET_1024 / _512 replace the two block targets of the split-K launches
-// SPLITK_C4 / SPLITK_LIN: the weight gradients of the 4x4/stride-2 convolutions / of the Linear layers (targets of their own since
-// round 5: MVK_SPLITK_TARGET_C4, MVK_SPLITK_TARGET_LIN)
-enum { SPLITK_C4 = 1025, SPLITK_LIN = 1026 };
-static int splitk_target(int t) {
-  static int t1024 = -1, t512 = -1, tc4 = -1, tlin = -1;
-  if (t1024 < 0) {
-    const char* a = mvk_tune("MVK_SPLITK_TARGET_1024");
-    const char* b = mvk_tune("MVK_SPLITK_TARGET_512");
-    const char* c = mvk_tune("MVK_SPLITK_TARGET_C4");
-    const char* l = mvk_tune("MVK_SPLITK_TARGET_LIN");
-    t1024 = a ? atoi(a) : 768;  // one full wave of 3 workgroups per CU (A/B in the step: 1.955 vs 1.969 ms at 1024)
-    t512 = b ? atoi(b) : 512;
-    // 4x4/stride-2 weight gradients at the encoder batch sit on the step's last dependent chain, beside the ordered finish of the
-    // decoders' partial sums: 256 workgroups (16 tiles x 16 slices at 64 -> 128 channels, 4 x 64 at 32 -> 64) instead of 768 write a
-    // third of the partial tiles and leave the chip to their neighbours — headline 1.0005 -> 0.992 ms, MMVAE MnistSvhn 0.581 ->
-    // 0.548 ms (tools/lab/r05/gpu_r05_k2.sh / _m2.sh; 128 and 192 are slower again)
-    tc4 = c ? atoi(c) : 256;
-    tlin = l ? atoi(l) : t1024;
-  }
-  return t == 1024 ? t1024 : (t == 512 ? t512 : (t == SPLITK_C4 ? tc4 : (t == SPLITK_LIN ? tlin : t)));
-}
+// block targets of the split-K launches; SPLITK_C4 / SPLITK_LIN: the weight gradients of the 4x4/stride-2 convolutions / of the
+// Linear layers (targets of their own since round 5)
+enum {
+  SPLITK_1024 = 768,  // one full wave of 3 workgroups per CU (A/B in the step: 1.955 vs 1.969 ms at 1024)
+  SPLITK_512 = 512,
+  // 4x4/stride-2 weight gradients at the encoder batch sit on the step's last dependent chain, beside the ordered finish of the
+  // decoders' partial sums: 256 workgroups (16 tiles x 16 slices at 64 -> 128 channels, 4 x 64 at 32 -> 64) instead of 768 write a
+  // third of the partial tiles and leave the chip to their neighbours — headline 1.0005 -> 0.992 ms, MMVAE MnistSvhn 0.581 ->
+  // 0.548 ms (tools/lab/r05/gpu_r05_k2.sh / _m2.sh; 128 and 192 are slower again)
+  SPLITK_C4 = 256,
+  SPLITK_LIN = SPLITK_1024,
+};
 
 int launch_splitk(GemmDesc& d, float* ws, long long ws_floats, int target_blocks, hipStream_t s) {
-  target_blocks = splitk_target(target_blocks);
   int tm = (d.M + 127) / 128;
   int tn = (d.N <= 32) ? 1 : (d.N + 63) / 64;
   int tiles = tm * tn;
@@ -776,7 +759,7 @@ extern "C" {
 // tall-skinny / K-serial shapes: too few output tiles to fill 256 CUs -> split the reduction
 static int launch_auto(GemmDesc& d, float* ws, int64_t ws_floats, hipStream_t s) {
   long long tiles = (long long)((d.M + 127) / 128) * ((d.N + 63) / 64);
-  if (d.e.atomic || (ws && tiles < 128 && d.K >= 256)) return launch_splitk(d, ws, ws_floats, 512, s);
+  if (d.e.atomic || (ws && tiles < 128 && d.K >= 256)) return launch_splitk(d, ws, ws_floats, SPLITK_512, s);
   return launch_igemm(d, 1, s);
 }
 
@@ -790,11 +773,10 @@ int mvk_linear_fwd(const float* X, const float* W, const float* b, float* Y, int
   }
   // a few hundred rows (the encoders' hidden layers at the training batch): too few 128-row tiles for the tiled engine,
   // which then splits K and needs a second launch to reduce (47 us for 512 x 784 -> 400); one 16 x 16 tile per workgroup
-  static const int fewrows = mvk_tune("MVK_FEWROWS") ? atoi(mvk_tune("MVK_FEWROWS")) : 1024;
   // (with scratch the kernel splits long reductions over workgroups: 32 rows x 12544 features, the heads of the PolyMNIST ResNet
   // encoders, 57 -> ~10 us; the fat heads of the 64x64 ResNet encoder — 128 x 65536 -> 64, 4 M weights — measured SLOWER there
   // than on the tiled engine, cfg5 8.40 vs 8.34 ms, so the size limit stays)
-  if (M <= fewrows && K >= 64 && (long long)N * K <= (1 << 21)) {
+  if (M <= 1024 && K >= 64 && (long long)N * K <= (1 << 21)) {
     const int rc = heads_launch(X, W, b, Y, nullptr, nullptr, nullptr, M, N, K, 1, K, act, mvk_stream(stream), ws, ws_floats);
     if (rc != 1) return rc;
   }
@@ -1360,7 +1342,7 @@ static int conv3x3_wgrad_any(const float* X, const float* dY, float* dWref, floa
   d.M = 9 * Cin;
   d.N = Cout;
   d.K = n * H * W;
-  return launch_splitk(d, ws, ws_floats, 1024, mvk_stream(stream));
+  return launch_splitk(d, ws, ws_floats, SPLITK_1024, mvk_stream(stream));
 }
 
 // the implicit GEMM of a 4x4 / stride-2 weight gradient: dWref[cv][cu][4][4] += sum over positions U(window)^T V
@@ -1430,11 +1412,10 @@ int mvk_conv4s2_wgrad_pair(const float* U0, const float* V0, float* dW0, int h0,
                            void* stream) {
   if (!U0 || !V0 || !dW0 || !U1 || !V1 || !dW1 || n < 0) return MVK_EINVAL;
   hipStream_t s = mvk_stream(stream);
-  static const bool off = mvk_tune("MVK_WGRAD_PAIR") && atoi(mvk_tune("MVK_WGRAD_PAIR")) == 0;  // A/B: two launches
   GemmDesc d[2] = {conv4s2_wgrad_desc(U0, V0, dW0, n, h0, w0, Cu0, Cv0, 0, nullptr, MVK_ACT_NONE),
                    conv4s2_wgrad_desc(U1, V1, dW1, n, h1, w1, Cu1, Cv1, 0, nullptr, MVK_ACT_NONE)};
   int z[2] = {0, 0};
-  bool ok = !off && engine() == 1 && n > 0 && !(n / 4 >= imgconv_min_images());  // (large batches: the output-stationary kernel)
+  bool ok = engine() == 1 && n > 0 && !(n / 4 >= imgconv_min_images());  // (large batches: the output-stationary kernel)
   const long long lim = 1ll << 29;
   for (int i = 0; i < 2 && ok; ++i) {
     GemmDesc& g = d[i];
@@ -1442,13 +1423,13 @@ int mvk_conv4s2_wgrad_pair(const float* U0, const float* V0, float* dW0, int h0,
          (long long)g.a.H * g.a.W * g.a.C * ((long long)g.K / (g.a.OH * g.a.OW) + 1) < lim && (long long)g.K * g.N < lim;
     if (!ok) break;
     const int tiles = ((g.M + 127) / 128) * ((g.N + 63) / 64), ktiles = (g.K + BK - 1) / BK;
-    int splits = splitk_target(SPLITK_C4) / tiles;
+    int splits = SPLITK_C4 / tiles;
     splits = splits < 1 ? 1 : (splits > ktiles ? ktiles : splits);
     g.zmode = Z_SPLITK;
     g.ksplit_tiles = (ktiles + splits - 1) / splits;
     g.ksplit_tiles += g.ksplit_tiles & 1;
     z[i] = (ktiles + g.ksplit_tiles - 1) / g.ksplit_tiles;
-    ok = z[i] > 1 && (long long)tiles * z[i] >= bf_min_blocks() && defer_free(g.e.out);
+    ok = z[i] > 1 && (long long)tiles * z[i] >= BF_MIN_BLOCKS && defer_free(g.e.out);
   }
   if (ok) {
     float* slab0 = defer_scratch(d[0].e.out, (long long)z[0] * d[0].M * d[0].N, s);
@@ -1517,7 +1498,7 @@ int mvk_unflatten_wgrad(const float* Z, const float* dY, float* dWref, int n, in
   d.M = Cin;
   d.N = 16 * Cout;
   d.K = n;
-  return launch_splitk(d, ws, ws_floats, 512, mvk_stream(stream));
+  return launch_splitk(d, ws, ws_floats, SPLITK_512, mvk_stream(stream));
 }
 
 // Backward of the (embedding, log-covariance) heads in one launch + the ordered finishes of its row-group slabs.
@@ -1585,7 +1566,7 @@ int mvk_flatten_wgrad(const float* H, const float* dY, float* dWref, int n, int 
   d.M = 16 * Cu;
   d.N = Cv;
   d.K = n;
-  return launch_splitk(d, ws, ws_floats, 512, mvk_stream(stream));
+  return launch_splitk(d, ws, ws_floats, SPLITK_512, mvk_stream(stream));
 }
 
 }  // extern "C"

@@ -350,12 +350,10 @@ int heads_launch(const float* X, const float* W0, const float* b0, float* Y0, co
   a.w_sn = w_sn;
   const int heads = W1 ? 2 : 1;
   dim3 grid((M + 15) / 16, heads * a.tiles_per_head);
-  static const int nw_env = mvk_tune("MVK_HEADS_WAVES") ? atoi(mvk_tune("MVK_HEADS_WAVES")) : 0;  // A/B switch
-  // few tiles and a long reduction: split K over workgroups (MVK_HEADS_KSPLIT=0 switches it off)
-  static const int ksplit_on = mvk_tune("MVK_HEADS_KSPLIT") ? atoi(mvk_tune("MVK_HEADS_KSPLIT")) : 1;
+  // few tiles and a long reduction: split K over workgroups
   const int tiles = (int)(grid.x * grid.y);
   int nz = 1;
-  if (ksplit_on && ws && tiles <= 64 && K >= 2048) {
+  if (ws && tiles <= 64 && K >= 2048) {
     nz = K / 256;                                   // >= 256 k per slice: one pass of 16 waves x 16
     const int cap = tiles >= 32 ? 64 : 128;         // ~2-4 k workgroups at most
     if (nz > cap) nz = cap;
@@ -363,8 +361,7 @@ int heads_launch(const float* X, const float* W0, const float* b0, float* Y0, co
     nz = (K + a.kz - 1) / a.kz;
     if (nz < 2 || (long long)nz * heads * M * N > ws_floats) nz = 1;
   }
-  static const int narrow_on = mvk_tune("MVK_NARROW_FWD") ? atoi(mvk_tune("MVK_NARROW_FWD")) : 1;  // A/B: 0 = the two-tile grid
-  if (narrow_on && heads == 1 && N > 16 && N <= 32 && M >= 1024) {  // many rows, one head: both column tiles in one workgroup
+  if (heads == 1 && N > 16 && N <= 32 && M >= 1024) {  // many rows, one head: both column tiles in one workgroup
     hipLaunchKernelGGL(narrow_fwd_kernel, dim3((M + 15) / 16), dim3(256), 0, s, a);
     MVK_CHECK_LAUNCH();
     return MVK_OK;
@@ -379,7 +376,7 @@ int heads_launch(const float* X, const float* W0, const float* b0, float* Y0, co
     MVK_CHECK_LAUNCH();
     return MVK_OK;
   }
-  if (nw_env ? nw_env == 16 : K >= 1024)
+  if (K >= 1024)
     hipLaunchKernelGGL(heads_fwd_kernel<16>, grid, dim3(1024), 0, s, a);
   else
     hipLaunchKernelGGL(heads_fwd_kernel<4>, grid, dim3(256), 0, s, a);
@@ -549,23 +546,19 @@ namespace mvk {
 // 1: shape not covered (the caller continues with the tiled engine)
 int smallk_fwd(const float* X, const float* W, long long w_sk, long long w_sn, const float* bias, int bias_mod, int act,
                float* Y, int M, int N, int K, hipStream_t s, const float* mask_src, int mask_act, int accumulate, float* y_amax) {
-  static const int off = mvk_tune("MVK_SMALLK") ? atoi(mvk_tune("MVK_SMALLK")) == 0 : 0;
-  if (off || K > 32 || K < 1 || N % 4 != 0 || N < 4 || !mvk_aligned16(Y) || M < 1 || (mask_src && !mvk_aligned16(mask_src)))
+  if (K > 32 || K < 1 || N % 4 != 0 || N < 4 || !mvk_aligned16(Y) || M < 1 || (mask_src && !mvk_aligned16(mask_src)))
     return 1;
   SmallKArgs a{X, W, bias, Y, M, N, K, bias_mod > 0 ? bias_mod : 1, act, w_sk, w_sn, mask_src, mask_act, accumulate, y_amax};
   const int CT = N / 4, ctb = CT < 256 ? CT : 256;
   const int gy = (CT + ctb - 1) / ctb;
-  static const int r_env = mvk_tune("MVK_SMALLK_ROWS") ? atoi(mvk_tune("MVK_SMALLK_ROWS")) : 0;
-  const long long want = r_env > 0 ? r_env : ((long long)M * gy + 255) / 256;  // rows per workgroup for ~256 workgroups
+  const long long want = ((long long)M * gy + 255) / 256;  // rows per workgroup for ~256 workgroups
   // measured at M = 5120, N = 2048, K = 20: 8 rows 19.2 us, 16 rows 18.0, 24 rows 20.4, 40 rows 28.8 (one wave per SIMD: latency-bound)
-  const int R = r_env > 0 ? (want <= 8 ? 8 : (want <= 16 ? 16 : (want <= 24 ? 24 : 40))) : (want <= 8 ? 8 : 16);
+  const int R = want <= 8 ? 8 : 16;
   const dim3 grid((M + R - 1) / R, gy);
 #define MVK_SMALLK_CASE(K4_)                                                                                    \
   case K4_:                                                                                                     \
     if (R == 8) hipLaunchKernelGGL((smallk_fwd_kernel<K4_, 8>), grid, dim3(256), 0, s, a);                      \
-    else if (R == 16) hipLaunchKernelGGL((smallk_fwd_kernel<K4_, 16>), grid, dim3(256), 0, s, a);               \
-    else if (R == 24) hipLaunchKernelGGL((smallk_fwd_kernel<K4_, 24>), grid, dim3(256), 0, s, a);               \
-    else hipLaunchKernelGGL((smallk_fwd_kernel<K4_, 40>), grid, dim3(256), 0, s, a);                            \
+    else hipLaunchKernelGGL((smallk_fwd_kernel<K4_, 16>), grid, dim3(256), 0, s, a);                            \
     break;
   switch ((K + 3) / 4 > 8 ? 8 : (K + 3) / 4) {
     MVK_SMALLK_CASE(1) MVK_SMALLK_CASE(2) MVK_SMALLK_CASE(3) MVK_SMALLK_CASE(4)

@@ -1666,8 +1666,7 @@ static int launch_bwd(const float* dU, const float* Uout, int u_act, const float
 #define MVK_SUB_LAUNCH(PU_, OCC_, UA_, VA_, UNITS_, DENSE_)                                                               \
   hipLaunchKernelGGL((small_up_bwd_kernel<CU, CV, NT, PU_, OCC_, UA_, VA_, DENSE_>), dim3(grid), dim3(NT), lds, s, dU, Uout, \
                      u_act, V, v_act, Wref, dV, ws, n, h, w, UNITS_, prof)
-  static const int dense_env = mvk_tune("MVK_SMALL_BWD_DENSE") ? atoi(mvk_tune("MVK_SMALL_BWD_DENSE")) : 1;  // A/B switch
-  const bool dense = dense_env && h == 16 && w == 16 && NT == 256 && mvk_aligned16(dU) && mvk_aligned16(Uout);
+  const bool dense = h == 16 && w == 16 && NT == 256 && mvk_aligned16(dU) && mvk_aligned16(Uout);
   if (units == 2 && occ_env == 4) {
     if (spec) MVK_SUB_LAUNCH(128, 4, MVK_ACT_SIGMOID, MVK_ACT_RELU, 2, false);
     else MVK_SUB_LAUNCH(128, 4, -1, -1, 2, false);

@@ -61,10 +61,6 @@ def to_bf3(x):
     return out
 
 
-# MVK_WGRAD_PAIR=0: the convolutional encoder's two inner weight gradients as two launches inside the backward-data chain (A/B)
-WGRAD_PAIR = _lib.tune("MVK_WGRAD_PAIR", "1") != "0"
-
-
 # =====================================================================================================
 # thin launch helpers (no autograd)
 # =====================================================================================================
@@ -157,7 +153,7 @@ def heads_fwd(h2, w_mu, b_mu, w_lv, b_lv, N, w_sk, w_sn):
     return mu, lv
 
 
-HEADS_BWD = _lib.tune("MVK_HEADS_BWD", "1") != "0"  # A/B switch: the heads' backward in one launch
+# The heads' backward in one launch (heads_bwd).
 # MEASURED (headline step, one box, 3-4 rounds each): 1.355 ms with the six separate launches, 1.326 ms with the fused launch
 # for the convolutional (SVHN) encoder only, 1.343 ms with the fused launch for the MLP encoder too (its chain is not the
 # critical one and the fused launch delays the other stream's kernels).  RE-MEASURED at the end of round 2, with the partial
@@ -189,7 +185,7 @@ def heads_bwd(x, x_act, dys, ws_, bs, w_sk, w_sn, flat_c=0, want_dx=True, prev_b
     (dx or None, [grad for autograd per weight], [grad per bias], grad for prev_bias)."""
     M, K = x.shape
     N = dys[0].shape[1]
-    if not HEADS_BWD or N > 32 or K % 16 != 0 or len(dys) > 2 or M < 1 or (M + 127) // 128 > 64:
+    if N > 32 or K % 16 != 0 or len(dys) > 2 or M < 1 or (M + 127) // 128 > 64:
         return None
     dw_params = ws_ if dw_params is None else dw_params
     tw, rw = zip(*[_grad_target(p) for p in dw_params])
@@ -415,10 +411,6 @@ def conv_up(V, wup, bias, n, h, w, Cu, Cv, act=NONE, u_nchw=False, u_act_src=Non
 LEAKY = ACT["leaky_relu_0.2"]
 
 
-# MVK_C3_Y_AMAX=0: the image-side 3x3 launches do not publish max |Y| (an mvk_amax pass computes it where needed; A/B)
-C3_Y_AMAX = _lib.tune("MVK_C3_Y_AMAX", "1") != "0"
-
-
 def conv3x3(X, wpack, bias, n, H, W, Cin, Cout, act=NONE, y_act_src=None, y_src_act=NONE, out_bias=None, res=None,
             res_alpha=1.0, y_amax=None):
     """3x3/1/1 convolution on NHWC (forward with the forward pack; backward data with the backward pack and Cin/Cout
@@ -601,10 +593,7 @@ def upsample2_bwd(dy, n, H, W, C):
 
 
 # ---- noise with the generator state in device memory (mvk_device_rng) -------------------------------------------------
-# MVK_DEVICE_RNG=0: draw from torch's generator instead (two extra host-issued fill launches per hipGraph replay).
-DEVICE_RNG = _lib.tune("MVK_DEVICE_RNG", "1") != "0"
-
-
+# (torch's generator would cost two extra host-issued fill launches per hipGraph replay)
 def _rng_state(device):
     """The device-resident generator state, tied to torch's CUDA generator of that device: re-seeded from its seed whenever
     torch was re-seeded since the last draw.  A re-seed is seen as a changed seed or an offset that went backwards — every
@@ -1167,8 +1156,7 @@ class SVHNEncoderFn(Function):
         # training batch each is a split-K GEMM of 256 workgroups and ~35 us, and the four launches were one dependent chain
         # (the step's last one).  Only where both targets are views of the flat gradient buffer inside deferred_reductions (the
         # pair's slabs live in the arena).
-        pair = (WGRAD_PAIR and schedule.scope(x.device) is not None and _is_direct(w1) and _is_direct(w2)
-                and x.device.type == "cuda")
+        pair = schedule.scope(x.device) is not None and _is_direct(w1) and _is_direct(w2) and x.device.type == "cuda"
         if not pair:
             dw2 = conv_wgrad(h2, dh3, w2, B, H // 8, W // 8, ch[2], ch[3])
         if fused is None:
@@ -1194,12 +1182,6 @@ class SVHNEncoderFn(Function):
 
 # MVK_TAIL_F16=0: the fused SVHN tail on bf16 pieces (small_up_fwd_bf_kernel) also where the scaled-fp16 chain runs
 TAIL_F16 = _lib.tune("MVK_TAIL_F16", "1") != "0"
-# MVK_C3_SPLIT256=0: 3x3 layers with 256 input channels stay on the tiled engine (A/B of mvk_conv3x3_s_part)
-C3_SPLIT256 = _lib.tune("MVK_C3_SPLIT256", "1") != "0"
-# MVK_C3_DUAL=0: a post-activation ResNet block forms its sum in an elementwise pass behind conv2 (A/B of mvk_conv3x3_s2)
-C3_DUAL = _lib.tune("MVK_C3_DUAL", "1") != "0"
-# MVK_TAIL_BWD_F16=0: the image layer's backward stays on bf16 pieces (small_up_bwd_bf_kernel) where its forward runs the scaled form
-TAIL_BWD_F16 = _lib.tune("MVK_TAIL_BWD_F16", "1") != "0"
 
 
 class SVHNDecoderFn(Function):
@@ -1249,7 +1231,7 @@ class SVHNDecoderFn(Function):
             a1, a2 = pool.take(), pool.take()
             a3 = pool.take() if (TAIL_F16 and nll_x is not None) else None  # bound of g3 for the image layer's scaled form
             # bound of the fused tail's stored gradient: the image layer's backward scales it (small_up_bwd_h_kernel)
-            ctx.a_dpre = pool.take() if (a3 is not None and TAIL_BWD_F16) else None
+            ctx.a_dpre = pool.take() if a3 is not None else None
             ctx.a_g3 = a3
             ctx.bslots = (pool.take(), pool.take())  # the backward pass's two slots: no fill launch there
             g1 = _new((n, 16 * C1), z2) if rot is None else rot.buf(rkey + ("g1",), (n, 16 * C1))
@@ -1276,12 +1258,10 @@ class SVHNDecoderFn(Function):
             rows = _new((n,), z2)
             # the stored gradient is pre-multiplied by nll_weight, the weight the rows are expected to enter the loss with
             ctx.nll_weight = float(nll_weight)
-            if a3 is not None and ctx.a_dpre is not None:  # ... and the maximum of the stored gradient published for the backward
+            if a3 is not None:  # scaled fp16 pairs under the bound the 64 -> 32 launch published (small_up_fwd_h_kernel), and the
+                # maximum of the stored gradient published for the backward
                 call("mvk_conv4s2_small_up_fwd_nll_sy", ptr(g3), ptr(w3), ptr(b3), ptr(nll_x), nll_x.shape[0], float(nll_scale),
                      float(nll_weight), ptr(out), ptr(rows), n, 16, 16, C4, C3, SIGMOID, ptr(a3), ptr(ctx.a_dpre), stream_ptr())
-            elif a3 is not None:  # scaled fp16 pairs under the bound the 64 -> 32 launch published (small_up_fwd_h_kernel)
-                call("mvk_conv4s2_small_up_fwd_nll_s", ptr(g3), ptr(w3), ptr(b3), ptr(nll_x), nll_x.shape[0], float(nll_scale),
-                     float(nll_weight), ptr(out), ptr(rows), n, 16, 16, C4, C3, SIGMOID, ptr(a3), stream_ptr())
             else:
                 call("mvk_conv4s2_small_up_fwd_nll_w", ptr(g3), ptr(w3), ptr(b3), ptr(nll_x), nll_x.shape[0], float(nll_scale),
                      float(nll_weight), ptr(out), ptr(rows), n, 16, 16, C4, C3, SIGMOID, stream_ptr())
@@ -1464,7 +1444,7 @@ def _rs_conv(pool, X, xam, wpack, bias, n, H, W, Cin, Cout, **kw):
         xam = xam if xam is not None else amax_of(X, pool.take())
         yam = pool.take()
         return conv3x3_s(X, wpack, bias, n, H, W, Cin, Cout, xam, w_am, yam, **kw), yam
-    if (C3_SPLIT256 and pool is not None and w_am is not None and Cin == 256 and kw.get("res") is None
+    if (pool is not None and w_am is not None and Cin == 256 and kw.get("res") is None
             and kw.get("act", NONE) != SIGMOID and kw.get("y_src_act", NONE) != SIGMOID and conv3x3_scaled_ok(n, H, W, 128, Cout)):
         # 256 input channels: more weights than a register-stationary wave holds — two launches over 128-channel slices
         xam = xam if xam is not None else amax_of(X, pool.take())
@@ -1475,7 +1455,7 @@ def _rs_conv(pool, X, xam, wpack, bias, n, H, W, Cin, Cout, **kw):
         return conv3x3_f(X, wpack, bias, n, H, W, Cin, Cout, **kw), None
     kw.pop("x_act", None)
     kw.pop("pre_scale", None)
-    if pool is not None and Cin <= 4 and Cout % 4 == 0 and kw.get("res") is None and C3_Y_AMAX:
+    if pool is not None and Cin <= 4 and Cout % 4 == 0 and kw.get("res") is None:
         # an image on the input side (conv_img of an encoder, the backward-data pass of a decoder's conv_img): the direct
         # kernel publishes max |Y| itself — the stack behind it takes the scaled-fp16 form without an amax pass over Y
         yam = pool.take()
@@ -1563,8 +1543,7 @@ class ResnetStackFn(Function):
                     a0 = h
                     a1, a1am = _rs_conv(pool, a0, ham, packs[iw1][0], b1, n, H, W, C, Chid, act=LEAKY)
                     w2am = getattr(packs[iw2][0], "mvk_amax", None)
-                    if (C3_DUAL and pool is not None and a1am is not None and w2am is not None
-                            and conv3x3_scaled_ok(n, H, W, Chid, Cout)):
+                    if pool is not None and a1am is not None and w2am is not None and conv3x3_scaled_ok(n, H, W, Chid, Cout):
                         # conv2, its LeakyReLU and the block's sum in one launch; y2 (the backward pass needs its signs) is the
                         # launch's second store, max |out| its published bound
                         xs = h if isc is None else linear_fwd(h.view(-1, C), params[isc].view(Cout, C), None, NONE).view(n, H, W, Cout)

@@ -12,7 +12,7 @@ from typing import Union
 
 import torch
 
-from ... import _lib, kernels, schedule
+from ... import kernels, schedule
 from ..base import BaseMultiVAE
 from ..base.base_utils import ModelOutput
 from .mopoe_config import MoPoEConfig
@@ -48,7 +48,7 @@ class MoPoE(BaseMultiVAE):
         self._sel_cache = {}
         # decoders that can score their own output (`reconstruction_nll`, e.g. Decoder_VAE_SVHN) do so in the epilogue of their
         # last layer; False = always decode + the generic likelihood kernel (A/B, and what every user-written decoder gets)
-        self.fused_decoder_tail = _lib.tune("MVK_FUSED_TAIL", "1") != "0"
+        self.fused_decoder_tail = True
         if self.multiple_latent_spaces:  # default multi-latent MLPs (mopoe_model.py:58-75)
             from ..nn.default_architectures import BaseDictDecodersMultiLatents, BaseDictEncoders_MultiLatents
 
@@ -132,7 +132,7 @@ class MoPoE(BaseMultiVAE):
     def _posterior(self, inputs, K, noise=None, choice=None, want_stats=False):
         early = {}
         x0 = next(iter(inputs.data.values()))
-        if noise is None and x0.is_cuda and kernels.DEVICE_RNG and schedule.BRANCH_STREAMS and len(self.encoders) > 1 \
+        if noise is None and x0.is_cuda and schedule.BRANCH_STREAMS and len(self.encoders) > 1 \
                 and x0.dim() > 1:
             # the noise does not depend on the encoders: its launch rides at the head of the short encoder's branch stream
             # instead of sitting between the encoders and the posterior kernel on the main one

@@ -213,8 +213,8 @@ class Nexus(BaseMultiVAE):
 
     @staticmethod
     def _uniforms(shape, device):
-        """U[0, 1) for the dropout decisions: the device generator (a replayed graph draws fresh subsets) unless it is off."""
-        if torch.device(device).type == "cuda" and kernels.DEVICE_RNG:
+        """U[0, 1) for the dropout decisions: the device generator (a replayed graph draws fresh subsets) on a CUDA device."""
+        if torch.device(device).type == "cuda":
             return kernels.device_randn(tuple(shape), device, uniform=True, lo=0.0, hi=1.0)
         return torch.rand(shape, device=device, dtype=torch.float32)
 

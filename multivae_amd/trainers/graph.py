@@ -190,7 +190,7 @@ class GraphedStep:
                                              and s.shape == d.shape and s.is_contiguous() and d.is_contiguous()
                                              and (d.numel() * d.element_size()) % 16 == 0 and d.data_ptr() % 16 == 0
                                              and s.data_ptr() % 16 == 0)]
-        if 2 <= len(fast) <= 8 and len(fast) == len(pairs) and os.environ.get("MVK_TWO_BLITS") != "1":  # (the switch: A/B only)
+        if 2 <= len(fast) <= 8 and len(fast) == len(pairs):
             descs = (_lib.CopyDesc * len(fast))()
             for e, (d, s) in zip(descs, fast):
                 e.dst, e.src, e.bytes = d.data_ptr(), s.data_ptr(), d.numel() * d.element_size()
