@@ -136,6 +136,41 @@ int mvk_cond_latent_bwd(const float* mu, const float* lv, const float* pmu, cons
                         const float* dzc, const float* gkl, int K, int B, int L, int C, float* dmu, float* dlv,
                         float* dpmu, float* dplv, void* stream);
 
+/* MHVAE level (models/mhvae/mhvae_model.py:119-184 subset_encode, base_utils.py:122-130 poe, :111-119 kl_divergence): for every
+ * subset s < S of the modalities, row b and element f, the product of the subset's available experts and the prior, one sample
+ * and the KL to the prior, in ONE launch for all subsets of a level of the hierarchy.  Experts j of (s, b): the e < E with bit e of
+ * member[s] set and masks[e][b] != 0, and the prior (always):
+ *   T_j = 1 / (exp(lv_j) + 1e-8);   P = sum_j T_j;   jmu = sum_j mu_j T_j / P;   jlv = log(1 / P);
+ *   z[s,b,f] = jmu + exp(jlv / 2) eps[s,b,f]   (eps NULL: z = jmu, the reference's return_mean);
+ *   kl_rows[s,b] = sum_f 1/2 (plv - jlv + exp(jlv - plv) + (jmu - pmu)^2 / exp(plv) - 1)   (no 1e-8 in the KL).
+ * A masked-out expert has T = 0 (the reference's log-variance of +inf, :88-101): nothing of it is read and its gradients are zeros.
+ * mu, lv: HOST arrays of E device pointers, 1 <= E <= MVK_MAX_MODALITIES; masks: HOST array of E device uint8 [B] pointers
+ * (entries may be NULL = all available) or NULL; member: HOST array of S bitmasks, 1 <= S <= MVK_MHVAE_MAX_SUBSETS, each non-zero
+ * and below 2^E, every expert in at least one.  The host tables are copied into the launch: the call is capturable.  Two layouts,
+ * anything else is MVK_EINVAL:
+ *   shared = 1  every mu[e], lv[e] is [B,F] and serves each subset that holds e; pmu = plv = NULL: the prior is N(0, I), an expert
+ *               with T = 1 / (1 + 1e-8) (the deepest level, :126-143);
+ *   shared = 0  mu[e], lv[e] are [S_e,B,F], one block per subset holding e, in increasing subset order; pmu, plv [S,B,F], both
+ *               required (the lower levels, :150-184, where every posterior depends on the subset's own z).
+ * eps, z [S,B,F]; kl_rows [S,B]; F = the flattened per-row size of the level's latent, S B (F + 1) < 2^38.  16-byte accesses when F % 4 == 0 and every
+ * pointer is 16-byte aligned, scalar ones otherwise.  No atomics: the row sums are taken in a fixed order, the result is
+ * bit-reproducible.  B = 0 is MVK_OK and writes nothing.
+ * bwd: dz [S,B,F] (nullable), gkl [S,B] (nullable) -> dmu[e], dlv[e] (HOST arrays of E device pointers, the shapes of mu[e], lv[e]),
+ * dpmu, dplv [S,B,F] (NULL exactly when pmu is NULL), all OVERWRITTEN, everything recomputed from the forward's inputs.  With
+ * a_j = T_j / P, vp = exp(plv):
+ *   G_mu = dz + gkl (jmu - pmu) / vp;          G_P = -1/2 dz eps P^(-3/2) + 1/2 gkl (1 / P - 1 / (P^2 vp));
+ *   dT_j = G_mu (mu_j - jmu) / P + G_P;        dmu_j = G_mu a_j;        dlv_j = -dT_j exp(lv_j) T_j^2;
+ *   dpmu = (as an expert) - gkl (jmu - pmu) / vp;      dplv = (as an expert) + 1/2 gkl (1 - 1 / (P vp) - (jmu - pmu)^2 / vp).
+ * shared = 1: the gradient of expert e at (b, f) is the sum over the subsets holding e, taken in increasing s in registers. */
+#define MVK_MHVAE_MAX_SUBSETS 255 /* subsets of one mvk_mhvae_level_* call (2^8 - 1: every non-empty subset of 8 modalities) */
+int mvk_mhvae_level_fwd(const float* const* mu, const float* const* lv, const uint8_t* const* masks, int E,
+                        const int32_t* member, int S, int shared, const float* pmu, const float* plv, const float* eps, int B,
+                        int F, float* z, float* kl_rows, void* stream);
+int mvk_mhvae_level_bwd(const float* const* mu, const float* const* lv, const uint8_t* const* masks, int E,
+                        const int32_t* member, int S, int shared, const float* pmu, const float* plv, const float* eps,
+                        const float* dz, const float* gkl, int B, int F, float* const* dmu, float* const* dlv, float* dpmu,
+                        float* dplv, void* stream);
+
 /* MVAE (models/mvae/mvae_model.py:56-118): for each of the S subsets of the objective (subset_bits: HOST array, bit m
  * = modality m), the product of the AVAILABLE experts of the subset and the N(0,I) prior in the log-sum-exp form of
  * `stable_poe` (base_utils.py:133-147; a missing modality has log-variance +inf, mvae_model.py:71-75), one sample

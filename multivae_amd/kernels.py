@@ -2105,6 +2105,71 @@ class CondLatentFn(Function):
         return (None, dmu, dlv, dpmu, dplv, None) + (None,) * ctx.n_cond
 
 
+class MHVAELevelFn(Function):
+    """One level of the MHVAE hierarchy for all S subsets (mvk_mhvae_level_fwd/bwd): the product of each subset's available
+    experts and the prior, one sample and the KL to the prior -> z [S,B,F], kl_rows [S,B].
+    member: S bitmasks over the E experts; masks: None or E entries (bool [B] or None); eps [S,B,F] or None (z = the mean).
+    shared=True: expert e is (mu, lv) of B F elements, the prior is N(0, I) (pmu = plv = None); shared=False: expert e holds S_e B F
+    elements, one block per subset holding it in increasing subset order, the prior pmu, plv S B F.  experts = mu_0, lv_0, mu_1,
+    lv_1, ...: any shape with that many elements; every one and the prior get a gradient of their own shape."""
+
+    @staticmethod
+    def forward(ctx, eps, member, shared, masks, B, F, pmu, plv, *experts):
+        mus, lvs = [_c(t) for t in experts[0::2]], [_c(t) for t in experts[1::2]]
+        E, S = len(mus), len(member)
+        if len(lvs) != E or E < 1:
+            raise ValueError("MHVAELevelFn: the experts are given as (mu, lv) pairs")
+        if (pmu is None) != (plv is None) or (pmu is None) != bool(shared):
+            raise ValueError("MHVAELevelFn: the shared layout takes no prior, the per-subset layout needs one")
+        pmu, plv = (None, None) if pmu is None else (_c(pmu), _c(plv))
+        eps = None if eps is None else _c(eps)
+        for e in range(E):
+            n = (1 if shared else sum(1 for m in member if m >> e & 1)) * B * F
+            if mus[e].numel() != n or lvs[e].numel() != n:
+                raise ValueError(f"MHVAELevelFn: expert {e} holds {mus[e].numel()} / {lvs[e].numel()} elements, expected {n}")
+        for t in (pmu, plv, eps):
+            if t is not None and t.numel() != S * B * F:
+                raise ValueError(f"MHVAELevelFn: the prior and eps hold S B F = {S * B * F} elements")
+        if masks is not None:
+            masks = [None if m is None else m.to(torch.bool).contiguous() for m in masks]
+        marr = ptr_array(masks) if masks is not None else None
+        mem = (C.c_int32 * S)(*[int(m) for m in member])
+        z = _new((S, B, F), mus[0])
+        kl = _new((S, B), mus[0])
+        call("mvk_mhvae_level_fwd", ptr_array(mus), ptr_array(lvs), marr, E, mem, S, int(bool(shared)), ptr(pmu), ptr(plv),
+             ptr(eps), B, F, ptr(z), ptr(kl), stream_ptr())
+        ctx.save_for_backward(*mus, *lvs, *(() if pmu is None else (pmu, plv)), *(() if eps is None else (eps,)))
+        ctx.masks = masks
+        ctx.cfg = (E, S, bool(shared), B, F, tuple(int(m) for m in member), pmu is not None, eps is not None)
+        ctx.shapes = [t.shape for t in experts]
+        return z, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, dkl):
+        E, S, shared, B, F, member, has_prior, has_eps = ctx.cfg
+        saved = ctx.saved_tensors
+        dev = saved[0].device
+        schedule.wait_loss(dev)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(dev)
+        mus, lvs = list(saved[:E]), list(saved[E:2 * E])
+        rest = list(saved[2 * E:])
+        pmu, plv = (rest.pop(0), rest.pop(0)) if has_prior else (None, None)
+        eps = rest.pop(0) if has_eps else None
+        dz = _c(dz) if dz is not None else None
+        dkl = _c(dkl) if dkl is not None else None
+        dmus, dlvs = [torch.empty_like(t) for t in mus], [torch.empty_like(t) for t in lvs]
+        dpmu, dplv = (None, None) if pmu is None else (torch.empty_like(pmu), torch.empty_like(plv))
+        marr = ptr_array(ctx.masks) if ctx.masks is not None else None
+        mem = (C.c_int32 * S)(*member)
+        call("mvk_mhvae_level_bwd", ptr_array(mus), ptr_array(lvs), marr, E, mem, S, int(shared), ptr(pmu), ptr(plv), ptr(eps),
+             ptr(dz), ptr(dkl), B, F, ptr_array(dmus), ptr_array(dlvs), ptr(dpmu), ptr(dplv), stream_ptr())
+        grads = []
+        for e in range(E):
+            grads += [dmus[e].view(ctx.shapes[2 * e]), dlvs[e].view(ctx.shapes[2 * e + 1])]
+        return (None, None, None, None, None, None, dpmu, dplv, *grads)
+
+
 class NexusAggregateFn(Function):
     """msgs_m [B, D] -> (agg [B, D], keep [B, M]): the Nexus message mean over the kept modalities (mvk_nexus_aggregate_fwd/bwd,
     nexus_model.py:209-254).  Keep set: masks (list of M bool [B]), keep_in [B, M], or FPD from u [B, M + 1] uniforms on [0, 1)
