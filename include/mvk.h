@@ -171,6 +171,23 @@ int mvk_mhvae_level_bwd(const float* const* mu, const float* const* lv, const ui
                         const float* dz, const float* gkl, int B, int F, float* const* dmu, float* const* dlv, float* dpmu,
                         float* dplv, void* stream);
 
+/* TELBO stage two (models/telbo/telbo_model.py:101-124): the samples of all M unimodal posteriors and the reference's row "KL",
+ * which takes the JOINT encoder's log-variance in the place of the modality's own, in ONE launch for all modalities:
+ *   z[m,b,l]      = mu_m[b,l] + exp(lv_m[b,l] / 2) eps[m,b,l];
+ *   kld_rows[m,b] = -1/2 sum_l (1 + joint_lv[b,l] - mu_m[b,l]^2 - exp(lv_m[b,l])).
+ * joint_lv [B,L]; mu, lv: HOST arrays of M device pointers ([B,L] each), 1 <= M <= MVK_MAX_MODALITIES, copied into the launch (the
+ * call is capturable); eps, z [M,B,L]; kld_rows [M,B].  Any L >= 1.  No atomics: a row sum is taken in a fixed order, the result
+ * is bit-reproducible.  B = 0 is MVK_OK and writes nothing; a bad argument is MVK_EINVAL before any launch.
+ * bwd: dz [M,B,L] (nullable), gkld [M,B] (nullable) -> dmu[m], dlv[m] [B,L] (HOST arrays of M device pointers) and djoint_lv [B,L]
+ * (nullable: not wanted), all OVERWRITTEN, everything recomputed from the forward's inputs:
+ *   dmu_m = dz_m + gkld[m,b] mu_m;     dlv_m = 1/2 exp(lv_m / 2) eps_m dz_m + 1/2 gkld[m,b] exp(lv_m);
+ *   djoint_lv[b,l] = -1/2 sum_m gkld[m,b]   (added in increasing m). */
+int mvk_telbo_latent_fwd(const float* joint_lv, const float* const* mu, const float* const* lv, int M, const float* eps,
+                         int B, int L, float* z, float* kld_rows, void* stream);
+int mvk_telbo_latent_bwd(const float* const* mu, const float* const* lv, int M, const float* eps, const float* dz,
+                         const float* gkld, int B, int L, float* const* dmu, float* const* dlv, float* djoint_lv,
+                         void* stream);
+
 /* MVAE (models/mvae/mvae_model.py:56-118): for each of the S subsets of the objective (subset_bits: HOST array, bit m
  * = modality m), the product of the AVAILABLE experts of the subset and the N(0,I) prior in the log-sum-exp form of
  * `stable_poe` (base_utils.py:133-147; a missing modality has log-variance +inf, mvae_model.py:71-75), one sample

@@ -183,6 +183,8 @@ PROTOTYPES = {
     "mvk_cond_latent_bwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "mvk_mhvae_level_fwd": [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p],
     "mvk_mhvae_level_bwd": [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
+    "mvk_telbo_latent_fwd": [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p],
+    "mvk_telbo_latent_bwd": [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p],
     "mvk_iwae_sample": [_p, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_logw": [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_reduce": [_p, _i, _i, _i, _p, _p],

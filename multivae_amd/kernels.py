@@ -2061,6 +2061,54 @@ class GaussSampleKLFn(Function):
         return None, dmu, dlv
 
 
+class TELBOLatentFn(Function):
+    """TELBO stage two: eps [M,B,L], the joint encoder's log-variance [B,L], unimodal (mu_m, lv_m)_m -> kld_rows [M,B], z_0 [B,L],
+    ..., z_{M-1} (the M slabs of the kernel's z [M,B,L]) with kld_rows[m,b] = -1/2 sum_l (1 + joint_lv - mu_m^2 - exp(lv_m))
+    (telbo_model.py:110-120; mvk_telbo_latent_fwd/bwd).  joint_lv gets a gradient only when it asks for one (the model hands in
+    a tensor without autograd: djoint_lv = NULL)."""
+
+    @staticmethod
+    def forward(ctx, eps, jlv, *mus_lvs):
+        M = len(mus_lvs) // 2
+        eps, jlv = _c(eps), _c(jlv)
+        mus = [_c(t) for t in mus_lvs[:M]]
+        lvs = [_c(t) for t in mus_lvs[M:]]
+        Me, B, L = eps.shape
+        if Me != M or len(mus_lvs) != 2 * M or M < 1:
+            raise ValueError(f"TELBOLatentFn: eps holds {Me} modalities, {len(mus_lvs)} (mu, lv) tensors were given")
+        for t in [jlv, *mus, *lvs]:
+            if tuple(t.shape) != (B, L):
+                raise ValueError(f"TELBOLatentFn: expected [{B}, {L}] for every mean and log-variance, got {tuple(t.shape)}")
+        z = _new((M, B, L), eps)
+        kld = _new((M, B), eps)
+        call("mvk_telbo_latent_fwd", ptr(jlv), ptr_array(mus), ptr_array(lvs), M, ptr(eps), B, L, ptr(z), ptr(kld), stream_ptr())
+        ctx.save_for_backward(eps, *mus, *lvs)
+        ctx.M = M
+        ctx.want_jlv = ctx.needs_input_grad[1]
+        ctx.set_materialize_grads(False)
+        return (kld, *z.unbind(0))  # one decoder input per modality: no slice node (zero-fill + copy in backward) per decoder
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dkld, *dzs):
+        schedule.wait_loss(ctx.saved_tensors[0].device)  # the gradients of the KL rows come out of the loss assembly launch
+        schedule.late_ready(ctx.saved_tensors[0].device)
+        saved = ctx.saved_tensors
+        eps, M = saved[0], ctx.M
+        mus, lvs = saved[1 : 1 + M], saved[1 + M :]
+        _, B, L = eps.shape
+        dz = None
+        if any(g is not None for g in dzs):  # the decoders' input gradients, side by side again (one launch)
+            dz = torch.stack([g if g is not None else torch.zeros_like(mus[0]) for g in dzs])
+        gk = _c(dkld) if dkld is not None else None
+        dmus = [_new((B, L), eps) for _ in range(M)]
+        dlvs = [_new((B, L), eps) for _ in range(M)]
+        djlv = _new((B, L), eps) if ctx.want_jlv else None
+        call("mvk_telbo_latent_bwd", ptr_array(mus), ptr_array(lvs), M, ptr(eps), ptr(dz), ptr(gk), B, L, ptr_array(dmus),
+             ptr_array(dlvs), ptr(djlv), stream_ptr())
+        return (None, djlv, *dmus, *dlvs)
+
+
 class CondLatentFn(Function):
     """(mu, lv) [B,L], prior (pmu, plv) [B,L] or (None, None) = N(0, I), eps [K,B,L], conditioning pieces [B, ...] ->
     zc [K,B,L+C] (the samples beside the flattened conditioning data: the conditional decoder's input), kl_rows [B]

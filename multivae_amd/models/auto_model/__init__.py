@@ -4,12 +4,13 @@ reference load here and folders written by `BaseModel.save` load in the referenc
 import json
 import os
 
-from .. import CMVAE, CMVAEConfig, CRMVAE, CVAE, CVAEConfig, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig, MHVAE, MHVAEConfig
+from .. import CMVAE, CMVAEConfig, CRMVAE, CVAE, CVAEConfig, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig, MHVAE, MHVAEConfig, TELBO, TELBOConfig
 from ..base import BaseMultiVAEConfig
 
 _MODELS = {"JMVAEConfig": (JMVAE, JMVAEConfig), "MMVAEConfig": (MMVAE, MMVAEConfig), "MoPoEConfig": (MoPoE, MoPoEConfig),
            "MVTCAEConfig": (MVTCAE, MVTCAEConfig), "MVAEConfig": (MVAE, MVAEConfig), "CRMVAEConfig": (CRMVAE, CRMVAEConfig), "DMVAEConfig": (DMVAE, DMVAEConfig), "MMVAEPlusConfig": (MMVAEPlus, MMVAEPlusConfig),
-           "NexusConfig": (Nexus, NexusConfig), "CVAEConfig": (CVAE, CVAEConfig), "CMVAEConfig": (CMVAE, CMVAEConfig), "MHVAEConfig": (MHVAE, MHVAEConfig)}
+           "NexusConfig": (Nexus, NexusConfig), "CVAEConfig": (CVAE, CVAEConfig), "CMVAEConfig": (CMVAE, CMVAEConfig), "MHVAEConfig": (MHVAE, MHVAEConfig),
+           "TELBOConfig": (TELBO, TELBOConfig)}
 
 
 def _name(json_path):

@@ -187,6 +187,7 @@ class BaseTrainer:
                                "(no CPU compute path)")
         self.device = torch.device(self.device) if not isinstance(self.device, torch.device) else self.device
         self.checkpoint = checkpoint
+        self.checktrainer(model)
         if checkpoint is not None:
             model = type(model).load_from_folder(checkpoint)
         model = model.to(self.device)
@@ -237,11 +238,23 @@ class BaseTrainer:
                             "input data.\n"
                             f"Exception raised: {type(e)} with message: " + str(e)) from e
 
+    def checktrainer(self, model):
+        """A model that asks for optimizer resets trains in stages (base_trainer.py:155-162)."""
+        if len(getattr(model, "reset_optimizer_epochs", ())) != 0:
+            raise AttributeError(f"The model {self.model_name} has a 'reset_optimizer_epochs' attribute that is not empty. That "
+                                 "means that it requires multistage training and therefore you should use the "
+                                 "multivae_amd.trainers.MultistageTrainer instead of the BaseTrainer.")
+
     # -- optimizer / scheduler ---------------------------------------------------------------------------------
+    def _trainable_params(self):
+        """The parameters the flat buffers and the optimizer state are built over; None: every parameter that requires a
+        gradient.  (MultistageTrainer: the current stage's.)"""
+        return None
+
     def set_optimizer(self):
         cfg = self.training_config
         params = cfg.optimizer_params or {}
-        self.flat = FlatParams(self.model)
+        self.flat = FlatParams(self.model, params=self._trainable_params())
         if self.distributed:
             self.flat.broadcast(0)  # C1: one parameter broadcast from rank 0 (DDP.__init__ in the reference)
         fused_ok = cfg.optimizer_cls == "Adam" and cfg.use_fused_adam and \
@@ -396,6 +409,10 @@ class BaseTrainer:
         if gs is not None:
             gs.drain()
 
+    def prepare_train_step(self, epoch, best_train_loss, best_eval_loss):
+        """Changes between two epochs, such as resetting the optimizer and the best losses (base_trainer.py:444-448): none here."""
+        return best_train_loss, best_eval_loss
+
     def train_step(self, epoch: int):
         self.callback_handler.on_train_step_begin(training_config=self.training_config, train_loader=self.train_loader,
                                                   epoch=epoch, rank=self.rank)
@@ -472,6 +489,7 @@ class BaseTrainer:
         history = []
         for epoch in range(self.trained_epochs + 1, cfg.num_epochs + 1):
             self.callback_handler.on_epoch_begin(training_config=cfg, epoch=epoch)
+            self.best_train_loss, self.best_eval_loss = self.prepare_train_step(epoch, self.best_train_loss, self.best_eval_loss)
             metrics = {}
             epoch_train_loss, epoch_metrics = self.train_step(epoch)
             metrics["train_epoch_loss"] = epoch_train_loss

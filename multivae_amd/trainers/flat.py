@@ -13,9 +13,22 @@ from .. import _lib, kernels
 class FlatParams:
     ALIGN = 64  # floats
 
-    def __init__(self, model: torch.nn.Module):
+    def __init__(self, model: torch.nn.Module, params=None):
+        """params: the parameters the buffers are built over (default: every parameter that requires a gradient).  A model
+        that trains in stages (TELBO) names the ones that receive gradients in the current stage; every other parameter is left
+        out of the buffers and loses its `.grad`, so nothing accumulates into it and no optimizer — the fused Adam, which sees
+        the buffers only, or a torch one, which skips a parameter without a gradient — moves or decays it."""
         self.all_params = list(model.parameters())  # torch.optim indexes its state by position in this list
-        self.params = [p for p in self.all_params if p.requires_grad]
+        if params is None:
+            self.params = [p for p in self.all_params if p.requires_grad]
+        else:
+            want = {id(p) for p in params}
+            self.params = [p for p in self.all_params if id(p) in want]
+            if len(self.params) != len(want) or not all(p.requires_grad for p in self.params):
+                raise ValueError("params must be trainable parameters of the model")
+            for p in self.all_params:
+                if id(p) not in want:
+                    p.grad = None
         if not self.params:
             raise ValueError("model has no trainable parameters")
         # Parameters a module announces as `late_leaf_params()` (the decoders' weights whose gradients a rotated step produces
@@ -24,10 +37,11 @@ class FlatParams:
         # contiguous range each.  The layout inside the buffer is private: state dicts and `dense()` go by parameter.
         late_first, late_rest = [], []  # per announcing module: its FIRST entry (by convention the first layer's weight, the
         # one a rotation of the small leaves only moves) / the others; the first entries sit at the very end, together
+        mine = {id(p) for p in self.params}
         for mod in model.modules():
             announce = getattr(mod, "late_leaf_params", None)
             if announce is not None:
-                ps = [p for p in announce() if p.requires_grad]
+                ps = [p for p in announce() if id(p) in mine]
                 late_first += ps[:1]
                 late_rest += ps[1:]
         group = {id(p): 1 for p in late_rest}
@@ -284,13 +298,16 @@ class FusedAdam(torch.optim.Optimizer):
         """zero_grad_in_step: the update clears the gradient buffer as it reads it, and the `zero_grad()` of the next step
         becomes free (one launch and one pass over the buffer less per step).  For loops of the form zero_grad -> backward
         -> step (BaseTrainer, bench.py): a gradient written after `step()` and before the next `zero_grad()` would survive."""
-        self.flat = flat
         self.zero_grad_in_step = bool(zero_grad_in_step)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=bool(amsgrad))
         super().__init__(flat.all_params, defaults)
+        self._fresh_state(flat)
+
+    def _fresh_state(self, flat):
+        self.flat = flat
         self.m = torch.zeros_like(flat.flat)
         self.v = torch.zeros_like(flat.flat)
-        self.vmax = torch.zeros_like(flat.flat) if amsgrad else None
+        self.vmax = torch.zeros_like(flat.flat) if self.amsgrad else None
         self.step_count = 0
         self._dev_state = self._dev_scalars = self._dev_host = None  # the captured form (prepare_captured / step_captured)
         # the rotated form (trainers/graph.py GraphedStep(rotate=True)): ranges updated at the head of the NEXT replay
@@ -298,6 +315,18 @@ class FusedAdam(torch.optim.Optimizer):
         self._rot_main = None
         self._rot_scalars = None
         self._rot_dirty = False
+        self._rot_armed = False
+
+    def rebind(self, flat: FlatParams):
+        """Continue on other buffers of the SAME model (its trainable set changed: a multistage model froze a part) with the
+        state of a new optimizer — step 0, zero moments: what torch.optim.Adam holds for parameters that meet their first
+        gradient — and the parameter group as it is: the learning rate and whatever a scheduler keeps there carry on.  Every
+        captured graph of the old buffers is stale; a rotated step must have been drained."""
+        if self._rot_dirty:
+            raise RuntimeError("FusedAdam.rebind(): drain the rotated step first")
+        if [id(p) for p in flat.all_params] != [id(p) for p in self.flat.all_params]:
+            raise ValueError("FusedAdam.rebind(): the buffers belong to another model")
+        self._fresh_state(flat)
 
     # the hyper-parameters live in the parameter group (schedulers write `lr` there)
     def _g(self):
