@@ -188,6 +188,38 @@ int mvk_telbo_latent_bwd(const float* const* mu, const float* const* lv, int M, 
                          const float* gkld, int B, int L, float* const* dmu, float* const* dlv, float* djoint_lv,
                          void* stream);
 
+/* Masked autoregressive flows (MAF, models/nn/flows.py; JNF: models/jnf/jnf_model.py:165-183 `_compute_ljm`, :246-254 the inverse in
+ * `encode`, :286-330 `_compute_poe_posterior`).  A flow is n_blocks MADEs of n_hidden + 1 masked linear layers ([H,D], [H,H] ...,
+ * [2D,H]; ReLU between; "sequential" degrees); the masks are computed from indices (deg(k) = k % (D - 1)), never read, and a masked
+ * weight's value never reaches a result.  One block: u = (x - mu(x)) exp(-lv(x)); ladj -= sum_d lv_d; x' = flip(u).
+ * fp32 FMA, fixed summation order, no atomics: bit-reproducible.  2 <= D <= MVK_MAF_MAX_DIM, 1 <= H <= MVK_MAF_MAX_DIM,
+ * 1 <= n_hidden <= MVK_MAF_MAX_HIDDEN, 1 <= n_blocks <= MVK_MAF_MAX_BLOCKS, 1 <= M <= MVK_MAX_MODALITIES.
+ * W, b (and dW, db): HOST arrays of M * n_blocks * (n_hidden + 1) device pointers, entry (m * n_blocks + block) * (n_hidden + 1) +
+ * layer, each the torch layout [out, in] / [out]; copied into the launch (capturable, nothing is repacked).
+ * fwd: z [B,D] (shared by the M flows) -> z0 [M,B,D], ladj [M,B]; with mu0, lv0 (HOST arrays of M device pointers, [B,D] each; both
+ * or neither, and `rows` with them) also rows[m,b] = -( sum_l log N(z0; mu0, exp(lv0 / 2)) + ladj ): JNF's stage-two row term.
+ * ws (nullable: no backward will follow): M * n_blocks * B * (2 D + n_hidden H) floats; per (m, block) the block's input [B,D], its
+ * lv [B,D] and the n_hidden hidden activations [B,H].
+ * bwd: upstream grows [M,B] (needs mu0 / lv0), dz0 [M,B,D], dladj [M,B] (each nullable, at least one given), the forward's z0 and ws
+ * -> dmu0[m], dlv0[m] [B,D] OVERWRITTEN (with mu0 / lv0); dz [B,D] (nullable) OVERWRITTEN with the sum over m in increasing m;
+ * deltas (the size of ws; nullable when no weight gradient is wanted): the pre-activation gradients of every layer; dW, db
+ * (nullable; a null ENTRY skips that tensor) +=, summed over b in increasing order by a second launch, masked entries untouched.
+ * inverse (ONE flow: W, b hold n_blocks * (n_hidden + 1) pointers): y [R,D] -> x [R,D] with forward(x) = y, ladj [R] (nullable)
+ * = sum of lv over blocks and coordinates (minus the forward's).
+ * B = 0 / R = 0 is MVK_OK and writes nothing; a bad argument is MVK_EINVAL before any launch. */
+#define MVK_MAF_MAX_DIM 512
+#define MVK_MAF_MAX_HIDDEN 4
+#define MVK_MAF_MAX_BLOCKS 4
+int mvk_maf_fwd(const float* z, const float* const* W, const float* const* b, int M, int n_blocks, int n_hidden, int D, int H,
+                const float* const* mu0, const float* const* lv0, int B, float* z0, float* ladj, float* rows, float* ws,
+                void* stream);
+int mvk_maf_bwd(const float* const* W, int M, int n_blocks, int n_hidden, int D, int H, const float* const* mu0,
+                const float* const* lv0, const float* z0, const float* ws, const float* grows, const float* dz0,
+                const float* dladj, int B, float* const* dmu0, float* const* dlv0, float* dz, float* deltas, float* const* dW,
+                float* const* db, void* stream);
+int mvk_maf_inverse(const float* y, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int R,
+                    float* x, float* ladj, void* stream);
+
 /* MVAE (models/mvae/mvae_model.py:56-118): for each of the S subsets of the objective (subset_bits: HOST array, bit m
  * = modality m), the product of the AVAILABLE experts of the subset and the N(0,I) prior in the log-sum-exp form of
  * `stable_poe` (base_utils.py:133-147; a missing modality has log-variance +inf, mvae_model.py:71-75), one sample

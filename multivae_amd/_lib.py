@@ -45,6 +45,7 @@ FAMILY = {"normal": 0, "laplace_with_softmax": 1, "normal_with_softplus": 2}  # 
 MAX_MODALITIES = 8
 CMVAE_MAX_CLUSTERS = 128  # MVK_CMVAE_MAX_CLUSTERS
 CMVAE_MAX_LDS_FLOATS = 12288  # MVK_CMVAE_MAX_LDS_FLOATS
+MAF_MAX_DIM, MAF_MAX_HIDDEN, MAF_MAX_BLOCKS = 512, 4, 4  # MVK_MAF_MAX_DIM / _HIDDEN / _BLOCKS
 
 _p = C.c_void_p
 _i = C.c_int
@@ -185,6 +186,9 @@ PROTOTYPES = {
     "mvk_mhvae_level_bwd": [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p],
     "mvk_telbo_latent_fwd": [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p],
     "mvk_telbo_latent_bwd": [_p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p],
+    "mvk_maf_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p],
+    "mvk_maf_bwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mvk_maf_inverse": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
     "mvk_iwae_sample": [_p, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_logw": [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_reduce": [_p, _i, _i, _i, _p, _p],

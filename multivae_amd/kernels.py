@@ -2897,3 +2897,142 @@ def fd_finish(state, D, mean=None, cov=None, terms=None):
     terms = torch.empty(_lib.FD_TERMS, **f) if terms is None else terms
     call("mvk_fd_finish", ptr(state), D, ptr(mean), ptr(cov), ptr(terms), stream_ptr())
     return mean, cov, terms
+
+
+# =====================================================================================================
+# Masked autoregressive flows (models/nn/flows.py; JNF)
+# =====================================================================================================
+def maf_fused_ok(D, H, n_hidden, n_blocks, M=1):
+    """The shapes mvk_maf_fwd/bwd/inverse take (mvk.h MVK_MAF_MAX_*): anything else runs the torch flow modules.  At the sizes that
+    were timed (D = 20, H = 128: profiles/NOTES_jnf.md) all three fused entries are ahead of the modules; other shapes were not
+    timed, so the range is what the kernels can run."""
+    return (2 <= D <= _lib.MAF_MAX_DIM and 1 <= H <= _lib.MAF_MAX_DIM and 1 <= n_hidden <= _lib.MAF_MAX_HIDDEN
+            and 1 <= n_blocks <= _lib.MAF_MAX_BLOCKS and 1 <= M <= _lib.MAX_MODALITIES)
+
+
+def _maf_check(dims, Ws, bs, M):
+    n_blocks, n_hidden, D, H = dims
+    if not maf_fused_ok(D, H, n_hidden, n_blocks, M):
+        raise ValueError(f"maf: (D, H, hidden layers, blocks, flows) = {(D, H, n_hidden, n_blocks, M)} is outside the fused range")
+    nl = n_hidden + 1
+    if len(Ws) != M * n_blocks * nl or len(bs) != len(Ws):
+        raise ValueError(f"maf: expected {M * n_blocks * nl} weights and biases, got {len(Ws)} and {len(bs)}")
+    for i, (w, b) in enumerate(zip(Ws, bs)):
+        l = i % nl
+        shape = (H, D) if l == 0 else (2 * D, H) if l == n_hidden else (H, H)
+        if tuple(w.shape) != shape or tuple(b.shape) != shape[:1]:
+            raise ValueError(f"maf: layer {l} holds {tuple(w.shape)} / {tuple(b.shape)}, expected {shape} / {shape[:1]}")
+        _lib.require_gpu_tensor(w)
+        _lib.require_gpu_tensor(b)
+        if not (w.is_contiguous() and b.is_contiguous()):
+            raise ValueError("maf: weights and biases must be contiguous (they are read in place)")
+
+
+def maf_forward(z, dims, Ws, bs, mus=None, lvs=None, keep=True):
+    """All M flows of z [B,D] in one launch (mvk_maf_fwd).  dims = (n_blocks, n_hidden, D, H); Ws, bs: the M * n_blocks *
+    (n_hidden + 1) masked-linear weights and biases, flow-major.  -> z0 [M,B,D], ladj [M,B], rows [M,B] (None without the
+    posteriors mus / lvs), ws (what maf_backward needs; None with keep=False)."""
+    n_blocks, n_hidden, D, H = dims
+    M = len(Ws) // (n_blocks * (n_hidden + 1)) if n_blocks * (n_hidden + 1) else 0
+    _maf_check(dims, Ws, bs, M)
+    z = _c(z)
+    B = z.shape[0]
+    if tuple(z.shape) != (B, D):
+        raise ValueError(f"maf_forward: z is {tuple(z.shape)}, expected [B, {D}]")
+    if mus is not None:
+        mus, lvs = [_c(t) for t in mus], [_c(t) for t in lvs]
+        if len(mus) != M or len(lvs) != M or any(tuple(t.shape) != (B, D) for t in [*mus, *lvs]):
+            raise ValueError(f"maf_forward: expected {M} means and log-variances of shape [{B}, {D}]")
+    z0, ladj = _new((M, B, D), z), _new((M, B), z)
+    rows = _new((M, B), z) if mus is not None else None
+    ws = _new((M * n_blocks * B * (2 * D + n_hidden * H),), z) if keep else None
+    call("mvk_maf_fwd", ptr(z), ptr_array(Ws), ptr_array(bs), M, n_blocks, n_hidden, D, H,
+         None if mus is None else ptr_array(mus), None if mus is None else ptr_array(lvs), B, ptr(z0), ptr(ladj), ptr(rows),
+         ptr(ws), stream_ptr())
+    return z0, ladj, rows, ws
+
+
+def maf_backward(dims, Ws, z0, ws, mus=None, lvs=None, grows=None, dz0=None, dladj=None, want_dz=False, dWs=None, dbs=None):
+    """The backward of maf_forward (mvk_maf_bwd): one launch for the data gradients, one more when dWs / dbs (lists of
+    accumulation targets, None entries skipped) are given.  -> dmus, dlvs (lists, None without posteriors), dz [B,D] or None."""
+    n_blocks, n_hidden, D, H = dims
+    M, B = z0.shape[0], z0.shape[1]
+    dmus = dlvs = None
+    if mus is not None:
+        dmus, dlvs = [_new((B, D), z0) for _ in range(M)], [_new((B, D), z0) for _ in range(M)]
+    dz = _new((B, D), z0) if want_dz else None
+    want_w = dWs is not None and any(t is not None for t in [*dWs, *(dbs or [])])
+    deltas = torch.empty_like(ws) if want_w else None
+    call("mvk_maf_bwd", ptr_array(Ws), M, n_blocks, n_hidden, D, H, None if mus is None else ptr_array(mus),
+         None if mus is None else ptr_array(lvs), ptr(z0), ptr(ws), ptr(grows), ptr(dz0), ptr(dladj), B,
+         None if mus is None else ptr_array(dmus), None if mus is None else ptr_array(dlvs), ptr(dz), ptr(deltas),
+         ptr_array(dWs) if want_w else None, ptr_array(dbs) if want_w else None, stream_ptr())
+    return dmus, dlvs, dz
+
+
+def maf_inverse(y, dims, Ws, bs, want_ladj=False):
+    """x with flow(x) = y for ONE flow, y [R,D], in one launch (mvk_maf_inverse) -> x [R,D], ladj [R] or None."""
+    n_blocks, n_hidden, D, H = dims
+    _maf_check(dims, Ws, bs, 1)
+    y = _c(y)
+    R = y.shape[0]
+    if tuple(y.shape) != (R, D):
+        raise ValueError(f"maf_inverse: y is {tuple(y.shape)}, expected [R, {D}]")
+    x = _new((R, D), y)
+    ladj = _new((R,), y) if want_ladj else None
+    call("mvk_maf_inverse", ptr(y), ptr_array(Ws), ptr_array(bs), n_blocks, n_hidden, D, H, R, ptr(x), ptr(ladj), stream_ptr())
+    return x, ladj
+
+
+class MAFFlowsFn(Function):
+    """The M masked autoregressive flows of JNF on one shared input, forward in one launch and backward in two.
+    apply(dims, with_post, z, *tensors): dims = (n_blocks, n_hidden, D, H); z [B,D]; tensors = with_post ? (mu0_0..mu0_{M-1},
+    lv0_0..lv0_{M-1}) : (), then W, b of every layer, flow-major (the parameters themselves: their gradients accumulate the way
+    linear_bwd_weight's do, _grad_target).  -> rows [M,B] (None without posteriors), z0 [M,B,D], ladj [M,B];
+    rows[m,b] = -(sum_l log N(z0; mu0_m, exp(lv0_m / 2)) + ladj): the stage-two term of jnf_model.py:165-183."""
+
+    @staticmethod
+    def forward(ctx, dims, with_post, z, *tensors):
+        n_blocks, n_hidden, D, H = dims
+        nl = n_blocks * (n_hidden + 1)
+        n_post = 0
+        if with_post:
+            M = len(tensors) // (2 + 2 * nl)
+            n_post = 2 * M
+        params = tensors[n_post:]
+        Ws, bs = list(params[0::2]), list(params[1::2])
+        mus = [_c(t) for t in tensors[: n_post // 2]] if with_post else None
+        lvs = [_c(t) for t in tensors[n_post // 2 : n_post]] if with_post else None
+        z = _c(z)
+        z0, ladj, rows, ws = maf_forward(z, dims, Ws, bs, mus, lvs)
+        ctx.dims, ctx.with_post, ctx.n_post = dims, with_post, n_post
+        ctx.save_for_backward(z0, ws, *(mus or []), *(lvs or []), *params)
+        ctx.set_materialize_grads(False)
+        return rows, z0, ladj
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grows, dz0, dladj):
+        saved = ctx.saved_tensors
+        z0, ws = saved[0], saved[1]
+        schedule.wait_loss(z0.device)
+        schedule.late_ready(z0.device)
+        n_post = ctx.n_post
+        M = z0.shape[0]
+        mus = list(saved[2 : 2 + M]) if ctx.with_post else None
+        lvs = list(saved[2 + M : 2 + n_post]) if ctx.with_post else None
+        params = saved[2 + n_post :]
+        need = ctx.needs_input_grad
+        n_out = 3 + n_post + len(params)
+        if grows is None and dz0 is None and dladj is None:
+            return (None,) * n_out
+        Ws = list(params[0::2])
+        targets, rets = [], []
+        for i, p in enumerate(params):
+            t, r = _grad_target(p) if need[3 + n_post + i] else (None, None)
+            targets.append(t)
+            rets.append(r)
+        dmus, dlvs, dz = maf_backward(ctx.dims, Ws, z0, ws, mus, lvs, None if grows is None else _c(grows),
+                                      None if dz0 is None else _c(dz0), None if dladj is None else _c(dladj),
+                                      want_dz=need[2], dWs=targets[0::2], dbs=targets[1::2])
+        return (None, None, dz, *(dmus or []), *(dlvs or []), *rets)

@@ -13,7 +13,8 @@ from .cvae import CVAE, CVAEConfig
 from .cmvae import CMVAE, CMVAEConfig
 from .mhvae import MHVAE, MHVAEConfig
 from .telbo import TELBO, TELBOConfig
+from .jnf import JNF, JNFConfig
 from .auto_model import AutoConfig, AutoModel  # noqa: E402  (needs the model classes above)
 
 __all__ = ["BaseAEConfig", "BaseMultiVAE", "BaseMultiVAEConfig", "ModelOutput", "MMVAE", "MMVAEConfig", "MoPoE",
-           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig", "CVAE", "CVAEConfig", "CMVAE", "CMVAEConfig", "MHVAE", "MHVAEConfig", "TELBO", "TELBOConfig"]
+           "MoPoEConfig", "MVTCAE", "MVTCAEConfig", "JMVAE", "JMVAEConfig", "BaseJointModel", "BaseJointModelConfig", "MMVAEPlus", "MMVAEPlusConfig", "AutoModel", "AutoConfig", "MVAE", "MVAEConfig", "CRMVAE", "CRMVAEConfig", "DMVAE", "DMVAEConfig", "Nexus", "NexusConfig", "CVAE", "CVAEConfig", "CMVAE", "CMVAEConfig", "MHVAE", "MHVAEConfig", "TELBO", "TELBOConfig", "JNF", "JNFConfig"]

@@ -4,13 +4,13 @@ reference load here and folders written by `BaseModel.save` load in the referenc
 import json
 import os
 
-from .. import CMVAE, CMVAEConfig, CRMVAE, CVAE, CVAEConfig, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig, MHVAE, MHVAEConfig, TELBO, TELBOConfig
+from .. import CMVAE, CMVAEConfig, CRMVAE, CVAE, CVAEConfig, DMVAE, DMVAEConfig, JMVAE, MMVAE, MVAE, MVTCAE, CRMVAEConfig, JMVAEConfig, MVAEConfig, MMVAEConfig, MMVAEPlus, MMVAEPlusConfig, MoPoE, MoPoEConfig, MVTCAEConfig, Nexus, NexusConfig, MHVAE, MHVAEConfig, TELBO, TELBOConfig, JNF, JNFConfig
 from ..base import BaseMultiVAEConfig
 
 _MODELS = {"JMVAEConfig": (JMVAE, JMVAEConfig), "MMVAEConfig": (MMVAE, MMVAEConfig), "MoPoEConfig": (MoPoE, MoPoEConfig),
            "MVTCAEConfig": (MVTCAE, MVTCAEConfig), "MVAEConfig": (MVAE, MVAEConfig), "CRMVAEConfig": (CRMVAE, CRMVAEConfig), "DMVAEConfig": (DMVAE, DMVAEConfig), "MMVAEPlusConfig": (MMVAEPlus, MMVAEPlusConfig),
            "NexusConfig": (Nexus, NexusConfig), "CVAEConfig": (CVAE, CVAEConfig), "CMVAEConfig": (CMVAE, CMVAEConfig), "MHVAEConfig": (MHVAE, MHVAEConfig),
-           "TELBOConfig": (TELBO, TELBOConfig)}
+           "TELBOConfig": (TELBO, TELBOConfig), "JNFConfig": (JNF, JNFConfig)}
 
 
 def _name(json_path):

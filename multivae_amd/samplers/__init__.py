@@ -1,8 +1,8 @@
 """Samplers that generate from the latent space of a trained model (`multivae/samplers`): they are fitted on the training
 embeddings and hand `model.decode` a ModelOutput like the one `encode` / `generate_from_prior` return.  The flow samplers
-(MAFSampler, IAFSampler) need pythae's flow models and trainers and are not built; neither is JNF, the
-one model that needs the same flows (TELBO and the multistage trainer it shares with JNF are: `multivae_amd.models.TELBO`,
-`multivae_amd.trainers.MultistageTrainer`)."""
+(MAFSampler, IAFSampler) are not built: they no longer lack a flow — `multivae_amd.models.nn.flows.MAF`,
+the module JNF's posteriors run on, with its fused kernels — but they fit it with a flow trainer, which is not here (and IAF is
+not)."""
 from .base import BaseSampler, BaseSamplerConfig
 from .gaussian_mixture import GaussianMixtureSampler, GaussianMixtureSamplerConfig
 
