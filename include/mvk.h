@@ -220,6 +220,27 @@ int mvk_maf_bwd(const float* const* W, int M, int n_blocks, int n_hidden, int D,
 int mvk_maf_inverse(const float* y, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int R,
                     float* x, float* ladj, void* stream);
 
+/* Inverse autoregressive flow (IAF, models/nn/flows.py) for the flow samplers (samplers/iaf_sampler): ONE flow of the MADEs above
+ * run the other way round, with the limits, pointer tables (n_blocks * (n_hidden + 1) entries), numeric contract, error codes and
+ * B = 0 behaviour of mvk_maf_*.  With (m, s) = MADE(y), one block: y_i = (x_i - m_i(y)) exp(-s_i(y)) for i = 0..D-1 from y = 0,
+ * ladj -= s_i; x' = flip(y).  The D steps cost ONE pass over the weights per block (the schedule of mvk_maf_inverse).
+ * fwd: x [B,D] -> z0 [B,D], ladj [B]; rows [B] (nullable) = -( sum_d log N(z0_d; 0, 1) + ladj ), the flow's NLL row under N(0, I).
+ * ws (nullable: no backward will follow): n_blocks * B * (2 D + n_hidden H) floats; per block the MADE's input y [B,D] (the block's
+ * output before the flip), s [B,D] and the n_hidden hidden activations of MADE(y) [B,H].
+ * bwd: upstream grows [B], dz0 [B,D], dladj [B] (each nullable, at least one given), the forward's z0 and ws -> dx [B,D] (nullable)
+ * OVERWRITTEN; deltas (the size of ws; nullable when no weight gradient is wanted): the pre-activation gradients of every layer;
+ * dW, db (nullable; a null ENTRY skips that tensor) +=, summed over b by the weight launch of mvk_maf_bwd.  The block's Jacobian in
+ * y is lower triangular: one launch solves the transposed system coordinate by coordinate, interleaved with one MADE backward pass.
+ * inverse: y [R,D] -> x [R,D] with forward(x) = y, ladj [R] (nullable): one MADE pass per block (y = flip(y), x = y exp(s) + m,
+ * ladj += sum_d s_d). */
+int mvk_iaf_fwd(const float* x, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int B,
+                float* z0, float* ladj, float* rows, float* ws, void* stream);
+int mvk_iaf_bwd(const float* const* W, int n_blocks, int n_hidden, int D, int H, const float* z0, const float* ws,
+                const float* grows, const float* dz0, const float* dladj, int B, float* dx, float* deltas, float* const* dW,
+                float* const* db, void* stream);
+int mvk_iaf_inverse(const float* y, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int R,
+                    float* x, float* ladj, void* stream);
+
 /* MVAE (models/mvae/mvae_model.py:56-118): for each of the S subsets of the objective (subset_bits: HOST array, bit m
  * = modality m), the product of the AVAILABLE experts of the subset and the N(0,I) prior in the log-sum-exp form of
  * `stable_poe` (base_utils.py:133-147; a missing modality has log-variance +inf, mvae_model.py:71-75), one sample

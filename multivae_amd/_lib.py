@@ -189,6 +189,9 @@ PROTOTYPES = {
     "mvk_maf_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p],
     "mvk_maf_bwd": [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p],
     "mvk_maf_inverse": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
+    "mvk_iaf_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "mvk_iaf_bwd": [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p],
+    "mvk_iaf_inverse": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
     "mvk_iwae_sample": [_p, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_logw": [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p, _p],
     "mvk_iwae_reduce": [_p, _i, _i, _i, _p, _p],

@@ -1,5 +1,7 @@
 // Masked autoregressive flows (MAF: a stack of MADE blocks, models/nn/flows.py) for JNF (models/jnf/jnf_model.py): the flows of ALL
-// modalities forward in one launch, their backward in two, and the sequential inverse of one flow in one.
+// modalities forward in one launch, their backward in two, and the sequential inverse of one flow in one.  Further down, the same
+// MADEs run the other way round: the inverse autoregressive flow (IAF) of the flow samplers (samplers/iaf_sampler), ONE flow, its
+// sequential forward in one launch, its backward in two and its one-pass inverse in one.
 //
 // One MADE is n_hidden + 1 masked linear layers: [H,D], (n_hidden - 1) x [H,H], [2D,H], ReLU between them.  With deg(k) = k % (D - 1)
 // for a hidden unit k the masks are index arithmetic (degrees_ordering = "sequential"):
@@ -50,6 +52,9 @@ struct MafGPost {
 struct MafWB1 {
   const float* w[MAXL];
   const float* b[MAXL];
+};
+struct MafW1 {
+  const float* w[MAXL];
 };
 
 // floats one (flow, block) takes in the forward's workspace and in the deltas: [B,D] + [B,D] + n_hidden x [B,H]
@@ -460,6 +465,313 @@ __global__ __launch_bounds__(256) void maf_inverse_kernel(const MafWB1 net, cons
   if (ladj && tid < RT && b0 + tid < R) ladj[b0 + tid] = lad[tid];
 }
 
+// ---- inverse autoregressive flow (IAF, models/nn/flows.py): ONE flow, the same MADEs run the other way round ------------------------
+// One block: y_i = (x_i - m_i(y)) exp(-s_i(y)) for i = 0..D-1 from y = 0, ladj -= s_i; x' = flip(y)   ((m, s) = MADE(y)).
+// Its inverse is one MADE pass: y = flip(y), x = y exp(s(y)) + m(y), ladj += sum_d s_d.
+
+// wave_dot down a COLUMN of a row-major matrix: (sum over k of pred(k) ? w[k * stride] * act[r * lda + k] : 0)
+template <class Pred>
+__device__ __forceinline__ float4 wave_dot_col(const float* __restrict__ w, int stride, const float* act, int lda, int K, int lane,
+                                               Pred pred) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int k = lane; k < K; k += 64) {
+    if (pred(k)) {
+      const float wv = w[(long long)k * stride];
+      a0 = fmaf(wv, act[k], a0);
+      a1 = fmaf(wv, act[lda + k], a1);
+      a2 = fmaf(wv, act[2 * lda + k], a2);
+      a3 = fmaf(wv, act[3 * lda + k], a3);
+    }
+  }
+  return make_float4(wave_sum_dpp(a0), wave_sum_dpp(a1), wave_sum_dpp(a2), wave_sum_dpp(a3));
+}
+
+// The schedule of maf_inverse_kernel: step i makes the hidden units of degree i - 1 of every layer final, then m_i, s_i and y_i.
+// LDS: xs [RT,D] | ys [RT,D] | ss [RT,D] | hs [nh][RT,H] | lad [RT] | deg [H]
+__global__ __launch_bounds__(256) void iaf_fwd_kernel(const MafWB1 net, const float* __restrict__ x, int nb, int nh, int D, int H,
+                                                      int B, float* __restrict__ z0, float* __restrict__ ladj,
+                                                      float* __restrict__ rows, float* __restrict__ ws) {
+  extern __shared__ float lds[];
+  float* xs = lds;
+  float* ys = xs + RT * D;
+  float* ss = ys + RT * D;
+  float* hs = ss + RT * D;
+  float* lad = hs + nh * RT * H;
+  int* deg = reinterpret_cast<int*>(lad + RT);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b0 = blockIdx.x * RT;
+  const int nl = nh + 1;
+  const long long CH = chunk_floats(B, D, H, nh);
+
+  for (int i = tid; i < RT * D; i += 256) {
+    const int r = i / D, c = i - r * D, b = b0 + r;
+    xs[i] = b < B ? x[(long long)b * D + c] : 0.f;
+  }
+  for (int k = tid; k < H; k += 256) deg[k] = k % (D - 1);
+  if (tid < RT) lad[tid] = 0.f;
+  __syncthreads();
+
+  float4 acc, acc2;
+  for (int blk = 0; blk < nb; ++blk) {
+    const int l0 = blk * nl;
+    // ys becomes y, coordinate by coordinate; what is read of it at step i (y_0 .. y_{i-1}) has been written by then
+    for (int i = 0; i < D; ++i) {
+      if (i > 0) {
+        const int g = i - 1;
+        for (int l = 0; l < nh; ++l) {
+          const float* __restrict__ W = net.w[l0 + l];
+          const float* __restrict__ bias = net.b[l0 + l];
+          float* out = hs + l * RT * H;
+          for (int o = g + wave * (D - 1); o < H; o += 4 * (D - 1)) {
+            if (l == 0)
+              acc = wave_dot(W + (long long)o * D, ys, D, D, lane, [=](int k) { return k <= g; });
+            else
+              acc = wave_dot(W + (long long)o * H, out - RT * H, H, H, lane, [=](int k) { return deg[k] <= g; });
+            if (lane < RT) out[lane * H + o] = fmaxf(pick(acc, lane) + bias[o], 0.f);
+          }
+          __syncthreads();
+        }
+      }
+      if (wave == 0) {
+        const float* __restrict__ W = net.w[l0 + nh];
+        const float* __restrict__ bias = net.b[l0 + nh];
+        const float* hl = hs + (nh - 1) * RT * H;
+        acc = wave_dot(W + (long long)i * H, hl, H, H, lane, [=](int k) { return deg[k] < i; });
+        acc2 = wave_dot(W + (long long)(D + i) * H, hl, H, H, lane, [=](int k) { return deg[k] < i; });
+        if (lane < RT) {
+          const float m = pick(acc, lane) + bias[i], s = pick(acc2, lane) + bias[D + i];
+          ys[lane * D + i] = (xs[lane * D + i] - m) * expf(-s);
+          ss[lane * D + i] = s;
+          lad[lane] -= s;
+        }
+      }
+      __syncthreads();
+    }
+    // every hidden unit (degrees 0 .. D - 2) is final: hs is MADE(y)'s hidden activations
+    if (ws) {
+      float* wsx = ws + (long long)blk * CH;
+      for (int i = tid; i < RT * D; i += 256) {
+        const int r = i / D, c = i - r * D, b = b0 + r;
+        if (b < B) {
+          wsx[(long long)b * D + c] = ys[i];
+          wsx[(long long)B * D + (long long)b * D + c] = ss[i];
+        }
+      }
+      for (int l = 0; l < nh; ++l) {
+        float* wh = wsx + 2LL * B * D + (long long)l * B * H;
+        for (int i = tid; i < RT * H; i += 256) {
+          const int r = i / H, c = i - r * H, b = b0 + r;
+          if (b < B) wh[(long long)b * H + c] = hs[l * RT * H + i];
+        }
+      }
+    }
+    for (int i = tid; i < RT * D; i += 256) {
+      const int r = i / D, c = i - r * D;
+      xs[r * D + (D - 1 - c)] = ys[i];
+    }
+    __syncthreads();
+  }
+
+  for (int i = tid; i < RT * D; i += 256) {
+    const int r = i / D, c = i - r * D, b = b0 + r;
+    if (b < B) z0[(long long)b * D + c] = xs[i];
+  }
+  const int b = b0 + wave;  // wave r finishes row r
+  if (b < B) {
+    if (lane == 0) ladj[b] = lad[wave];
+    if (rows) {
+      float s = 0.f;
+      for (int c = lane; c < D; c += 64) {
+        const float v = xs[wave * D + c];
+        s += -0.5f * (LOG_2PI + v * v);
+      }
+      s = wave_sum_dpp(s);
+      if (lane == 0) rows[b] = -(s + lad[wave]);
+    }
+  }
+}
+
+// The block's Jacobian in y is lower triangular (x_j = y_j exp(s_j(y)) + m_j(y)): the backward is a transposed triangular solve that
+// interleaves with ONE backward pass of the MADE.  i = D-1 .. 0: the deltas of the hidden units of degree i (they need the output
+// cotangents cm_j, cs_j of j > i only), last hidden layer first; v_i = the MADE's input gradient at coordinate i;
+// lam_i = exp(-s_i) (gy_i + v_i); cm_i = -lam_i; cs_i = -gl - lam_i y_i exp(s_i).  dx = lam.
+// LDS: g [RT,D] | c [RT,2D] | dl [nh][RT,H] | gl [RT] | deg [H]
+__global__ __launch_bounds__(256) void iaf_bwd_data_kernel(const MafW1 net, int nb, int nh, int D, int H, int B,
+                                                           const float* __restrict__ z0, const float* __restrict__ ws,
+                                                           const float* __restrict__ grows, const float* __restrict__ dz0,
+                                                           const float* __restrict__ dladj, float* __restrict__ dx,
+                                                           float* __restrict__ deltas) {
+  extern __shared__ float lds[];
+  float* g = lds;
+  float* c = g + RT * D;
+  float* dl = c + RT * 2 * D;
+  float* gl = dl + nh * RT * H;
+  int* deg = reinterpret_cast<int*>(gl + RT);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b0 = blockIdx.x * RT;
+  const int nl = nh + 1;
+  const long long CH = chunk_floats(B, D, H, nh);
+
+  for (int k = tid; k < H; k += 256) deg[k] = k % (D - 1);
+  // the gradient at the last block's y: z0 is that y flipped
+  for (int i = tid; i < RT * D; i += 256) {
+    const int r = i / D, cc = i - r * D, b = b0 + r;
+    float v = 0.f;
+    if (b < B) {
+      const long long at = (long long)b * D + (D - 1 - cc);
+      if (grows) v = grows[b] * z0[at];
+      if (dz0) v += dz0[at];
+    }
+    g[i] = v;
+  }
+  if (tid < RT) {
+    const int b = b0 + tid;
+    float v = 0.f;
+    if (b < B) {
+      if (grows) v = -grows[b];
+      if (dladj) v += dladj[b];
+    }
+    gl[tid] = v;
+  }
+  __syncthreads();
+
+  float4 acc;
+  for (int blk = nb - 1; blk >= 0; --blk) {
+    const int l0 = blk * nl;
+    const float* wsx = ws + (long long)blk * CH;
+    const float* wss = wsx + (long long)B * D;
+    const float* whs = wsx + 2LL * B * D;
+    for (int i = D - 1; i >= 0; --i) {
+      if (i < D - 1) {  // no hidden unit has degree D - 1
+        for (int l = nh - 1; l >= 0; --l) {
+          const float* __restrict__ W = net.w[l0 + l + 1];
+          const float* hl = whs + (long long)l * B * H;
+          float* out = dl + l * RT * H;
+          for (int o = i + wave * (D - 1); o < H; o += 4 * (D - 1)) {
+            if (l == nh - 1)
+              acc = wave_dot_col(W + o, H, c, 2 * D, 2 * D, lane, [=](int k) { return (k < D ? k : k - D) > i; });
+            else
+              acc = wave_dot_col(W + o, H, out + RT * H, H, H, lane, [=](int k) { return deg[k] >= i; });
+            if (lane < RT) {
+              const int b = b0 + lane;
+              out[lane * H + o] = b < B && hl[(long long)b * H + o] > 0.f ? pick(acc, lane) : 0.f;
+            }
+          }
+          __syncthreads();
+        }
+      }
+      if (wave == 0) {
+        acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < D - 1) acc = wave_dot_col(net.w[l0] + i, D, dl, H, H, lane, [=](int k) { return deg[k] >= i; });
+        if (lane < RT) {
+          const int b = b0 + lane;
+          float s = 0.f, y = 0.f;
+          if (b < B) {
+            s = wss[(long long)b * D + i];
+            y = wsx[(long long)b * D + i];
+          }
+          const float lam = expf(-s) * (g[lane * D + i] + pick(acc, lane));
+          g[lane * D + i] = lam;
+          c[lane * 2 * D + i] = -lam;
+          c[lane * 2 * D + D + i] = -gl[lane] - lam * (y * expf(s));
+        }
+      }
+      __syncthreads();
+    }
+    if (deltas) {
+      float* dlx = deltas + (long long)blk * CH;
+      for (int i = tid; i < RT * 2 * D; i += 256) {
+        const int r = i / (2 * D), b = b0 + r;
+        if (b < B) dlx[(long long)b * 2 * D + (i - r * 2 * D)] = c[i];
+      }
+      for (int l = 0; l < nh; ++l) {
+        float* dh = dlx + 2LL * B * D + (long long)l * B * H;
+        for (int i = tid; i < RT * H; i += 256) {
+          const int r = i / H, b = b0 + r;
+          if (b < B) dh[(long long)b * H + (i - r * H)] = dl[l * RT * H + i];
+        }
+      }
+    }
+    if (blk > 0) {  // the block's input is the previous block's y flipped; c is free once the deltas are out
+      __syncthreads();
+      for (int i = tid; i < RT * D; i += 256) {
+        const int r = i / D, cc = i - r * D;
+        c[r * D + (D - 1 - cc)] = g[i];
+      }
+      __syncthreads();
+      for (int i = tid; i < RT * D; i += 256) g[i] = c[i];
+      __syncthreads();
+    }
+  }
+  if (dx)
+    for (int i = tid; i < RT * D; i += 256) {
+      const int r = i / D, cc = i - r * D, b = b0 + r;
+      if (b < B) dx[(long long)b * D + cc] = g[i];
+    }
+}
+
+// LDS: xs [RT,D] | bufA [RT,S] | bufB [RT,S] | lad [RT] | deg [H]   (S = max(H, 2D))
+__global__ __launch_bounds__(256) void iaf_inverse_kernel(const MafWB1 net, const float* __restrict__ y, int nb, int nh, int D,
+                                                          int H, int R, float* __restrict__ x, float* __restrict__ ladj) {
+  extern __shared__ float lds[];
+  const int S = H > 2 * D ? H : 2 * D;
+  float* xs = lds;
+  float* bufA = xs + RT * D;
+  float* bufB = bufA + RT * S;
+  float* lad = bufB + RT * S;
+  int* deg = reinterpret_cast<int*>(lad + RT);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b0 = blockIdx.x * RT;
+  const int nl = nh + 1;
+
+  for (int i = tid; i < RT * D; i += 256) {  // flipped: the last block's input
+    const int r = i / D, c = i - r * D, b = b0 + r;
+    xs[r * D + (D - 1 - c)] = b < R ? y[(long long)b * D + c] : 0.f;
+  }
+  for (int k = tid; k < H; k += 256) deg[k] = k % (D - 1);
+  if (tid < RT) lad[tid] = 0.f;
+  __syncthreads();
+
+  for (int blk = nb - 1; blk >= 0; --blk) {
+    const int l0 = blk * nl;
+    const float* in = xs;
+    int ldi = D, K = D;
+    float* out = bufA;
+    for (int l = 0; l < nh; ++l) {
+      made_layer(net.w[l0 + l], net.b[l0 + l], in, ldi, K, out, H, H, l == 0 ? 0 : 1, D, deg);
+      __syncthreads();
+      in = out;
+      ldi = H;
+      K = H;
+      out = out == bufA ? bufB : bufA;
+    }
+    made_layer(net.w[l0 + nh], net.b[l0 + nh], in, ldi, K, out, 2 * D, 2 * D, 2, D, deg);
+    __syncthreads();
+    // y exp(s) + m into the buffer the last hidden layer no longer needs, flipped for the block that follows
+    float* tmp = out == bufA ? bufB : bufA;
+    for (int i = tid; i < RT * D; i += 256) {
+      const int r = i / D, c = i - r * D;
+      const float m = out[r * 2 * D + c], s = out[r * 2 * D + D + c];
+      tmp[r * D + (blk > 0 ? D - 1 - c : c)] = xs[i] * expf(s) + m;
+    }
+    {  // wave r: ladj[r] += sum_d s[r,d]
+      float s = 0.f;
+      for (int c = lane; c < D; c += 64) s += out[wave * 2 * D + D + c];
+      s = wave_sum_dpp(s);
+      if (lane == 0) lad[wave] += s;
+    }
+    __syncthreads();
+    for (int i = tid; i < RT * D; i += 256) xs[i] = tmp[i];
+    __syncthreads();
+  }
+
+  for (int i = tid; i < RT * D; i += 256) {
+    const int r = i / D, c = i - r * D, b = b0 + r;
+    if (b < R) x[(long long)b * D + c] = xs[i];
+  }
+  if (ladj && tid < RT && b0 + tid < R) ladj[b0 + tid] = lad[tid];
+}
+
 bool shape_ok(int M, int nb, int nh, int D, int H) {
   return M >= 1 && M <= MAXM && nb >= 1 && nb <= MVK_MAF_MAX_BLOCKS && nh >= 1 && nh <= MVK_MAF_MAX_HIDDEN && D >= 2 &&
          D <= MVK_MAF_MAX_DIM && H >= 1 && H <= MVK_MAF_MAX_DIM;
@@ -554,6 +866,72 @@ int mvk_maf_inverse(const float* y, const float* const* W, const float* const* b
   if (R == 0) return MVK_OK;
   const size_t lds = sizeof(float) * (2 * (size_t)RT * D + (size_t)n_hidden * RT * H + RT + H);
   hipLaunchKernelGGL(maf_inverse_kernel, dim3((R + RT - 1) / RT), dim3(256), lds, mvk_stream(stream), net, y, n_blocks, n_hidden,
+                     D, H, R, x, ladj);
+  MVK_CHECK_LAUNCH();
+  return MVK_OK;
+}
+
+int mvk_iaf_fwd(const float* x, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int B,
+                float* z0, float* ladj, float* rows, float* ws, void* stream) {
+  if (!x || !W || !b || !shape_ok(1, n_blocks, n_hidden, D, H) || B < 0 || !z0 || !ladj) return MVK_EINVAL;
+  const int nl = n_blocks * (n_hidden + 1);
+  MafWB1 net{};
+  for (int l = 0; l < nl; ++l) {
+    if (!W[l] || !b[l]) return MVK_EINVAL;
+    net.w[l] = W[l];
+    net.b[l] = b[l];
+  }
+  if (B == 0) return MVK_OK;
+  const size_t lds = sizeof(float) * (3 * (size_t)RT * D + (size_t)n_hidden * RT * H + RT + H);
+  hipLaunchKernelGGL(iaf_fwd_kernel, dim3((B + RT - 1) / RT), dim3(256), lds, mvk_stream(stream), net, x, n_blocks, n_hidden, D, H,
+                     B, z0, ladj, rows, ws);
+  MVK_CHECK_LAUNCH();
+  return MVK_OK;
+}
+
+int mvk_iaf_bwd(const float* const* W, int n_blocks, int n_hidden, int D, int H, const float* z0, const float* ws,
+                const float* grows, const float* dz0, const float* dladj, int B, float* dx, float* deltas, float* const* dW,
+                float* const* db, void* stream) {
+  if (!W || !shape_ok(1, n_blocks, n_hidden, D, H) || B < 0 || !z0 || !ws) return MVK_EINVAL;
+  if (!grows && !dz0 && !dladj) return MVK_EINVAL;  // nothing to propagate
+  if ((dW || db) && !deltas) return MVK_EINVAL;
+  const int nl = n_blocks * (n_hidden + 1);
+  MafW1 net{};
+  MafGW gw{};
+  for (int l = 0; l < nl; ++l) {
+    if (!W[l]) return MVK_EINVAL;
+    net.w[l] = W[l];
+    gw.w[l] = dW ? dW[l] : nullptr;  // a null entry: that layer's gradient is not wanted
+    gw.b[l] = db ? db[l] : nullptr;
+  }
+  if (B == 0) return MVK_OK;
+  const size_t lds = sizeof(float) * (3 * (size_t)RT * D + (size_t)n_hidden * RT * H + RT + H);
+  hipLaunchKernelGGL(iaf_bwd_data_kernel, dim3((B + RT - 1) / RT), dim3(256), lds, mvk_stream(stream), net, n_blocks, n_hidden, D, H,
+                     B, z0, ws, grows, dz0, dladj, dx, deltas);
+  MVK_CHECK_LAUNCH();
+  if (dW || db) {
+    const long long big = (long long)H * (H > 2 * D ? H : 2 * D);
+    hipLaunchKernelGGL(maf_bwd_weight_kernel, dim3((unsigned)((big + 255) / 256), nl), dim3(256), 0, mvk_stream(stream), gw,
+                       n_hidden, D, H, B, ws, deltas);
+    MVK_CHECK_LAUNCH();
+  }
+  return MVK_OK;
+}
+
+int mvk_iaf_inverse(const float* y, const float* const* W, const float* const* b, int n_blocks, int n_hidden, int D, int H, int R,
+                    float* x, float* ladj, void* stream) {
+  if (!y || !W || !b || !shape_ok(1, n_blocks, n_hidden, D, H) || R < 0 || !x) return MVK_EINVAL;
+  const int nl = n_blocks * (n_hidden + 1);
+  MafWB1 net{};
+  for (int l = 0; l < nl; ++l) {
+    if (!W[l] || !b[l]) return MVK_EINVAL;
+    net.w[l] = W[l];
+    net.b[l] = b[l];
+  }
+  if (R == 0) return MVK_OK;
+  const int S = H > 2 * D ? H : 2 * D;
+  const size_t lds = sizeof(float) * ((size_t)RT * D + 2 * (size_t)RT * S + RT + H);
+  hipLaunchKernelGGL(iaf_inverse_kernel, dim3((R + RT - 1) / RT), dim3(256), lds, mvk_stream(stream), net, y, n_blocks, n_hidden,
                      D, H, R, x, ladj);
   MVK_CHECK_LAUNCH();
   return MVK_OK;

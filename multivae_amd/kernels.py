@@ -2904,8 +2904,9 @@ def fd_finish(state, D, mean=None, cov=None, terms=None):
 # =====================================================================================================
 def maf_fused_ok(D, H, n_hidden, n_blocks, M=1):
     """The shapes mvk_maf_fwd/bwd/inverse take (mvk.h MVK_MAF_MAX_*): anything else runs the torch flow modules.  At the sizes that
-    were timed (D = 20, H = 128: profiles/NOTES_jnf.md) all three fused entries are ahead of the modules; other shapes were not
-    timed, so the range is what the kernels can run."""
+    were timed (D = 20, H = 128: profiles/NOTES_jnf.md; D = 20 and 64 as a sampler's fit step and inverse:
+    profiles/NOTES_flow_samplers.md) all three fused entries are ahead of the modules; other shapes were not timed, so the range is
+    what the kernels can run."""
     return (2 <= D <= _lib.MAF_MAX_DIM and 1 <= H <= _lib.MAF_MAX_DIM and 1 <= n_hidden <= _lib.MAF_MAX_HIDDEN
             and 1 <= n_blocks <= _lib.MAF_MAX_BLOCKS and 1 <= M <= _lib.MAX_MODALITIES)
 
@@ -3036,3 +3037,95 @@ class MAFFlowsFn(Function):
                                       None if dz0 is None else _c(dz0), None if dladj is None else _c(dladj),
                                       want_dz=need[2], dWs=targets[0::2], dbs=targets[1::2])
         return (None, None, dz, *(dmus or []), *(dlvs or []), *rets)
+
+
+# =====================================================================================================
+# Inverse autoregressive flow (models/nn/flows.py; the flow samplers)
+# =====================================================================================================
+def iaf_fused_ok(D, H, n_hidden, n_blocks):
+    """The shapes mvk_iaf_fwd/bwd/inverse take: those of maf_fused_ok for one flow; anything else runs the torch IAF module.  At the
+    sizes that were timed (D = 20 and 64, H = 128, 3 hidden layers, 2 blocks: profiles/NOTES_flow_samplers.md) the fit step and the
+    inverse are ahead of the module; other shapes were not timed, so the range is what the kernels can run."""
+    return maf_fused_ok(D, H, n_hidden, n_blocks, 1)
+
+
+def iaf_forward(x, dims, Ws, bs, want_rows=False, keep=True):
+    """ONE inverse autoregressive flow of x [B,D] in one launch (mvk_iaf_fwd).  dims = (n_blocks, n_hidden, D, H); Ws, bs: the
+    n_blocks * (n_hidden + 1) masked-linear weights and biases.  -> z0 [B,D], ladj [B], rows [B] (the NLL under N(0, I); None
+    unless want_rows), ws (what iaf_backward needs; None with keep=False)."""
+    n_blocks, n_hidden, D, H = dims
+    _maf_check(dims, Ws, bs, 1)
+    x = _c(x)
+    B = x.shape[0]
+    if tuple(x.shape) != (B, D):
+        raise ValueError(f"iaf_forward: x is {tuple(x.shape)}, expected [B, {D}]")
+    z0, ladj = _new((B, D), x), _new((B,), x)
+    rows = _new((B,), x) if want_rows else None
+    ws = _new((n_blocks * B * (2 * D + n_hidden * H),), x) if keep else None
+    call("mvk_iaf_fwd", ptr(x), ptr_array(Ws), ptr_array(bs), n_blocks, n_hidden, D, H, B, ptr(z0), ptr(ladj), ptr(rows), ptr(ws),
+         stream_ptr())
+    return z0, ladj, rows, ws
+
+
+def iaf_backward(dims, Ws, z0, ws, grows=None, dz0=None, dladj=None, want_dx=False, dWs=None, dbs=None, deltas=None):
+    """The backward of iaf_forward (mvk_iaf_bwd): one launch for the data gradient and the layers' deltas, one more when dWs / dbs
+    (lists of accumulation targets, None entries skipped) are given.  deltas: a buffer the size of ws to reuse.  -> dx [B,D] or
+    None."""
+    n_blocks, n_hidden, D, H = dims
+    B = z0.shape[0]
+    dx = _new((B, D), z0) if want_dx else None
+    want_w = dWs is not None and any(t is not None for t in [*dWs, *(dbs or [])])
+    if want_w and deltas is None:
+        deltas = torch.empty_like(ws)
+    call("mvk_iaf_bwd", ptr_array(Ws), n_blocks, n_hidden, D, H, ptr(z0), ptr(ws), ptr(grows), ptr(dz0), ptr(dladj), B, ptr(dx),
+         ptr(deltas) if want_w else None, ptr_array(dWs) if want_w else None, ptr_array(dbs) if want_w else None, stream_ptr())
+    return dx
+
+
+def iaf_inverse(y, dims, Ws, bs, want_ladj=False):
+    """x with flow(x) = y, y [R,D], in one launch and one MADE pass per block (mvk_iaf_inverse) -> x [R,D], ladj [R] or None."""
+    n_blocks, n_hidden, D, H = dims
+    _maf_check(dims, Ws, bs, 1)
+    y = _c(y)
+    R = y.shape[0]
+    if tuple(y.shape) != (R, D):
+        raise ValueError(f"iaf_inverse: y is {tuple(y.shape)}, expected [R, {D}]")
+    x = _new((R, D), y)
+    ladj = _new((R,), y) if want_ladj else None
+    call("mvk_iaf_inverse", ptr(y), ptr_array(Ws), ptr_array(bs), n_blocks, n_hidden, D, H, R, ptr(x), ptr(ladj), stream_ptr())
+    return x, ladj
+
+
+class IAFFlowFn(Function):
+    """One inverse autoregressive flow, forward in one launch and backward in two.  apply(dims, x, *params): dims = (n_blocks,
+    n_hidden, D, H); x [B,D]; params = W, b of every layer in order (the parameters themselves: their gradients accumulate the way
+    MAFFlowsFn's do, _grad_target).  -> rows [B] (the NLL under N(0, I)), z0 [B,D], ladj [B]."""
+
+    @staticmethod
+    def forward(ctx, dims, x, *params):
+        Ws, bs = list(params[0::2]), list(params[1::2])
+        z0, ladj, rows, ws = iaf_forward(x, dims, Ws, bs, want_rows=True)
+        ctx.dims = dims
+        ctx.save_for_backward(z0, ws, *params)
+        ctx.set_materialize_grads(False)
+        return rows, z0, ladj
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grows, dz0, dladj):
+        saved = ctx.saved_tensors
+        z0, ws, params = saved[0], saved[1], saved[2:]
+        schedule.wait_loss(z0.device)
+        schedule.late_ready(z0.device)
+        need = ctx.needs_input_grad
+        if grows is None and dz0 is None and dladj is None:
+            return (None,) * (2 + len(params))
+        targets, rets = [], []
+        for i, p in enumerate(params):
+            t, r = _grad_target(p) if need[2 + i] else (None, None)
+            targets.append(t)
+            rets.append(r)
+        dx = iaf_backward(ctx.dims, list(params[0::2]), z0, ws, None if grows is None else _c(grows),
+                          None if dz0 is None else _c(dz0), None if dladj is None else _c(dladj), want_dx=need[1],
+                          dWs=targets[0::2], dbs=targets[1::2])
+        return (None, dx, *rets)

@@ -1,10 +1,12 @@
-"""Normalizing flows: the masked autoregressive flow (MAF, Papamakarios et al. 2017) over MADE blocks (Germain et al. 2015), written
-from the published definition with the module layout and state-dict keys of `pythae.models.normalizing_flows` (`BaseNF`, `MADE`,
-`MAF`), which the reference's JNF takes its flows from.
+"""Normalizing flows: the masked autoregressive flow (MAF, Papamakarios et al. 2017) and the inverse autoregressive flow (IAF, Kingma
+et al. 2016) over MADE blocks (Germain et al. 2015), written from the published definitions with the module layout and state-dict
+keys of `pythae.models.normalizing_flows` (`BaseNF`, `MADE`, `MAF`, `IAF`), which the reference's JNF and flow samplers take their
+flows from.
 
 These modules are plain torch: they run on the CPU, and on the GPU they are the path for everything the fused kernels decline
 (`kernels.maf_fused_ok`, custom `BaseNF` flows).  JNF binds fusable `MAF`s to `mvk_maf_fwd/bwd/inverse` (csrc/maf.hip), which
-compute the masks from the degree formulas below instead of reading the `mask` buffers.
+compute the masks from the degree formulas below instead of reading the `mask` buffers; the flow samplers bind a fusable `IAF` to
+`mvk_iaf_fwd/bwd/inverse` in the same way.
 
 Degrees ("sequential" ordering), D = prod(input_dim): the inputs have m[-1] = arange(D), hidden layer i has m[i][k] = k % (D - 1).
 Hidden masks: mask_i[o, k] = m[i][o] >= m[i-1][k]; output mask [D, H]: mask[d, k] = m[last][k] < d, stacked twice ([2D, H]: the rows
@@ -58,6 +60,15 @@ class MADEConfig(BaseConfig):
 
 @dataclass
 class MAFConfig(BaseConfig):
+    input_dim: Union[Tuple[int, ...], None] = None
+    n_made_blocks: int = 2
+    n_hidden_in_made: int = 3
+    hidden_size: int = 128
+    include_batch_norm: bool = False
+
+
+@dataclass
+class IAFConfig(BaseConfig):
     input_dim: Union[Tuple[int, ...], None] = None
     n_made_blocks: int = 2
     n_hidden_in_made: int = 3
@@ -163,10 +174,60 @@ class MAF(BaseNF):
         return ModelOutput(out=y, log_abs_det_jac=sum_log_abs_det_jac)
 
 
-def fused_layout(flow):
-    """(D, H, n_hidden, n_blocks, [MaskedLinear of every block in order]) when `flow` is a MAF the fused kernels can stand in for —
-    the layer shapes they assume and `mask` buffers equal to the sequential masks they compute from indices — else None."""
-    if type(flow) is not MAF or len(flow.net) < 1:
+class IAF(BaseNF):
+    """Inverse autoregressive flow: the MADEs of a MAF run the other way round, so that `inverse` (sampling) is one MADE pass per
+    block and `forward` (the density) is the coordinate-by-coordinate sweep.  With (m, s) = MADE(.) (pythae: `mu`, `log_var`):
+    forward, per block in order, from y = 0: y[:, i] = (x[:, i] - m(y)[:, i]) exp(-s(y)[:, i]), ladj -= s(y)[:, i] for i = 0..D-1,
+    then x = y.flip(1).  Inverse, per block in reverse: y = y.flip(1); y = y exp(s(y)) + m(y); ladj += s.sum(-1)."""
+
+    def __init__(self, model_config: IAFConfig):
+        BaseNF.__init__(self)
+        if model_config.input_dim is None:
+            raise AttributeError("IAFConfig needs input_dim (a tuple): the network is built from it")
+        if model_config.include_batch_norm:
+            raise NotImplementedError("IAF: include_batch_norm=True is not built here")
+        self.model_config = model_config
+        self.model_name = "IAF"
+        self.input_dim = tuple(model_config.input_dim)
+        self.hidden_size = model_config.hidden_size
+        self.net = nn.ModuleList()
+        made_config = MADEConfig(input_dim=self.input_dim, output_dim=self.input_dim,
+                                 hidden_sizes=[self.hidden_size] * model_config.n_hidden_in_made,
+                                 degrees_ordering="sequential")
+        for _ in range(model_config.n_made_blocks):
+            self.net.append(MADE(made_config))
+
+    def forward(self, x: torch.Tensor, **kwargs) -> ModelOutput:
+        x = x.reshape(x.shape[0], -1)
+        D = x.shape[1]
+        sum_log_abs_det_jac = torch.zeros(x.shape[0], dtype=x.dtype, device=x.device)
+        for layer in self.net:
+            cols = []  # y_0 .. y_{i-1}; the MADE's outputs at i do not see the zeros behind them
+            for i in range(D):
+                y = torch.cat(cols + [x.new_zeros(x.shape[0], D - i)], dim=1) if cols else torch.zeros_like(x)
+                layer_out = layer(y)
+                mu, log_var = layer_out.mu, layer_out.log_var
+                cols.append(((x[:, i] - mu[:, i]) * (-log_var[:, i]).exp()).unsqueeze(1))
+                sum_log_abs_det_jac = sum_log_abs_det_jac - log_var[:, i]
+            x = torch.cat(cols, dim=1).flip(dims=(1,))
+        return ModelOutput(out=x, log_abs_det_jac=sum_log_abs_det_jac)
+
+    def inverse(self, y: torch.Tensor, **kwargs) -> ModelOutput:
+        y = y.reshape(y.shape[0], -1)
+        sum_log_abs_det_jac = torch.zeros(y.shape[0], dtype=y.dtype, device=y.device)
+        for layer in self.net[::-1]:
+            y = y.flip(dims=(1,))
+            layer_out = layer(y)
+            y = y * layer_out.log_var.exp() + layer_out.mu
+            sum_log_abs_det_jac = sum_log_abs_det_jac + layer_out.log_var.sum(dim=-1)
+        return ModelOutput(out=y, log_abs_det_jac=sum_log_abs_det_jac)
+
+
+def fused_layout(flow, kind=MAF):
+    """(D, H, n_hidden, n_blocks, [MaskedLinear of every block in order]) when `flow` is a flow of class `kind` (MAF or IAF) that the
+    fused kernels can stand in for — the layer shapes they assume and `mask` buffers equal to the sequential masks they compute from
+    indices — else None."""
+    if kind not in (MAF, IAF) or type(flow) is not kind or len(flow.net) < 1:
         return None
     D = int(np.prod(flow.input_dim))
     layers = []

@@ -1,9 +1,12 @@
 """Samplers that generate from the latent space of a trained model (`multivae/samplers`): they are fitted on the training
-embeddings and hand `model.decode` a ModelOutput like the one `encode` / `generate_from_prior` return.  The flow samplers
-(MAFSampler, IAFSampler) are not built: they no longer lack a flow — `multivae_amd.models.nn.flows.MAF`,
-the module JNF's posteriors run on, with its fused kernels — but they fit it with a flow trainer, which is not here (and IAF is
-not)."""
+embeddings and hand `model.decode` a ModelOutput like the one `encode` / `generate_from_prior` return.  GaussianMixtureSampler fits
+a mixture by fused EM; MAFSampler and IAFSampler fit one normalizing flow per latent space (`flow_fit.fit_flow`: on the fused flow
+kernels of csrc/maf.hip where they apply, else the torch flow modules) and sample by inverting it."""
 from .base import BaseSampler, BaseSamplerConfig
+from .flow_fit import fit_flow
 from .gaussian_mixture import GaussianMixtureSampler, GaussianMixtureSamplerConfig
+from .iaf_sampler import IAFSampler, IAFSamplerConfig
+from .maf_sampler import MAFSampler, MAFSamplerConfig
 
-__all__ = ["BaseSampler", "BaseSamplerConfig", "GaussianMixtureSampler", "GaussianMixtureSamplerConfig"]
+__all__ = ["BaseSampler", "BaseSamplerConfig", "GaussianMixtureSampler", "GaussianMixtureSamplerConfig", "MAFSampler",
+           "MAFSamplerConfig", "IAFSampler", "IAFSamplerConfig", "fit_flow"]
