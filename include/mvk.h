@@ -474,7 +474,8 @@ int mvk_iwae_sample(const float* loc, const float* sd, const float* noise, int K
  * per-data-point, per-chunk bodies of mopoe_model.py:524-588, mmvae_model.py:400-437, mvtcae_model.py:250-284 and
  * joint_model.py:113-148.  rows: HOST array of n_rows device pointers to [K,B] UNRESCALED NLL rows
  * (mvk_recon_nll_fwd with rescale = 1); loc, sd: HOST arrays of E <= MVK_IWAE_MAX_EXPERTS device pointers [B,L];
- * z [K,B,L]; lw [K,B]. */
+ * z [K,B,L]; lw [K,B].  Non-finite densities follow torch.logsumexp: an expert at -inf drops out of the mixture, all experts at
+ * -inf give lw = +inf, and a NaN expert density (sd = 0) gives lw = NaN for that (k,b). */
 int mvk_iwae_logw(const float* z, const float* const* rows, int n_rows, const float* const* loc,
                   const float* const* sd, int E, const float* prior_loc, const float* prior_sd, int K, int B, int L,
                   int family, float* lw, void* stream);
@@ -482,7 +483,7 @@ int mvk_iwae_logw(const float* z, const float* const* rows, int n_rows, const fl
 /* ll[b] = logsumexp over the n arrays lw[j][k,b] (k < K) - log(n K): the log-mean-exp of the importance weights
  * (the two-level logsumexp over K-chunks of the reference is the same number; MMVAE+ concatenates the weights of its
  * M conditioning modalities, mmvaePlus_model.py:521-525).  lw: HOST array of n <= MVK_MAX_MODALITIES device
- * pointers [K,B]; ll [B]. */
+ * pointers [K,B]; ll [B].  As torch.logsumexp: a column that is all -inf gives -inf, a +inf entry gives +inf, a NaN entry NaN. */
 int mvk_iwae_reduce(const float* const* lw, int n, int K, int B, float* ll, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -1026,7 +1027,11 @@ int mvk_nexus_aggregate_bwd(const float* keep, const float* g, int M, int B, int
  * else 1.  z, r, rows, masks (nullable), grows (entries nullable), dr: HOST arrays of device pointers; D, gamma, adapt: HOST
  * arrays.  q [M, B] (out: the row sums of (z - r)^2) and s2 [M] are kept for the backward pass; work: scratch of
  * M * ((B + 3) / 4) floats.  bwd: dr[m] [B, D_m] (overwritten) = d sum_b grows[m][b] rows[m][b] / d r_m, the path through s_m
- * included; z gets no gradient (it is detached).  Block sums are fixed-order two-stage reductions: deterministic. */
+ * included; z gets no gradient (it is detached).  Block sums are fixed-order two-stage reductions: deterministic.  masks[m] == NULL
+ * inside a given array means modality m is complete; grows[m] == NULL means a zero gradient (dr[m] = 0).  An adapted modality whose
+ * s2[m] comes out 0 (z_m == r_m, or differences so small that their squares underflow) is not special-cased: ln 0 and 1 / 0 give
+ * what the float32 formulas give, rows[m] and dr[m] all NaN (masked rows included), s2[m] = 0; the other modalities are not
+ * affected. */
 int mvk_nexus_top_nll_fwd(const float* const* z, const float* const* r, const uint8_t* const* masks, const int* D,
                           const float* gamma, const int* adapt, int M, int B, float* const* rows, float* q, float* s2,
                           float* work, void* stream);

@@ -418,6 +418,8 @@ __global__ __launch_bounds__(256) void iwae_logw_kernel(IwaePtrs a, const float*
       m = lq;
     } else if (lq > -INFINITY) {
       s += expf(lq - m);
+    } else if (lq != lq) {
+      s = lq;  // a NaN expert density fails both comparisons above: it must reach lw as torch.logsumexp would carry it
     }
   }
   const float lqz = m + logf(s) - logf((float)E);
@@ -438,10 +440,12 @@ __global__ __launch_bounds__(256) void iwae_reduce_kernel(IwaeLw a, int n, int K
   for (int j = 0; j < n; ++j)
     for (int k = lane; k < K; k += 64) m = fmaxf(m, a.lw[j][(long long)k * B + b]);
   m = wave_max(m);
+  // A column maximum of -inf or +inf is not subtracted (inf - inf): all -inf gives s = 0 and ll = -inf, a +inf entry s = +inf and
+  // ll = +inf, and a NaN entry, which fmaxf drops, reaches s here whatever the maximum is.
+  const float mm = (m > -INFINITY && m < INFINITY) ? m : 0.f;
   float s = 0.f;
-  if (m > -INFINITY)
-    for (int j = 0; j < n; ++j)
-      for (int k = lane; k < K; k += 64) s += expf(a.lw[j][(long long)k * B + b] - m);
+  for (int j = 0; j < n; ++j)
+    for (int k = lane; k < K; k += 64) s += expf(a.lw[j][(long long)k * B + b] - mm);
   s = wave_sum(s);
   if (lane == 0) ll[b] = m + logf(s) - logf((float)n * (float)K);
 }
