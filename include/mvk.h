@@ -1188,6 +1188,28 @@ int mvk_fd_begin(const float* X0, const float* X1, int64_t n, int D, void* state
 int mvk_fd_update(const float* X0, const float* X1, int64_t n, int D, void* state, void* stream);
 int mvk_fd_finish(void* state, int D, double* mean, double* cov, double* terms, void* stream);
 
+/* PolyMNIST classifier (multivae/metrics/classifiers/mmnist.py, eval mode: dropout is the identity) with what the coherence
+ * evaluator does with its logits, in one launch: x [n,3,28,28] fp32 contiguous -> conv 4x4 / stride 2 / padding 1 (10) + ReLU ->
+ * conv 4x4 / stride 2 / padding 1 (20) + ReLU -> flatten in (c, h, w) order -> 980 -> 128 + ReLU -> 10.  The weights are the
+ * module's parameters in PyTorch's layouts, read in place (no packed copy exists, so nothing has to be invalidated):
+ * w1 [10,3,4,4], b1 [10], w2 [20,10,4,4], b2 [20], w3 [128,980], b3 [128], w4 [10,128], b4 [10].
+ * Outputs, each may be NULL (not all three):
+ *   logits [n,10] fp32;
+ *   pred [n] int32 = torch.argmax(logits, 1): the first maximum, a NaN logit counting as the maximum;
+ *   counts [11,2] int64, ACCUMULATED (ClassCounts.update): row i has the label labels[i % label_rows] (int64; the sample-major
+ *   stacking of nb_samples_for_cross > 1 generations over label_rows data rows), r = the label, or 10 for a label outside
+ *   [0, 10): counts[r][0] += (pred == label), counts[r][1] += 1.  Integer atomics; there is no floating-point atomic.
+ * Every product and sum is fp32 (plain FMAs in the convolutions and fc2, the f32-input MFMA in fc1), each logit one fixed
+ * sequence of operations on its own image: the logits of an image are bit-identical from run to run, for every n and wherever
+ * the image falls among the mvk_polyclf_tile() images of a workgroup.  No activation goes to global memory.
+ * mvk_polyclf_tile: images per workgroup (not a status).
+ * n == 0 is MVK_OK and writes nothing.  MVK_EINVAL: n < 0; all three outputs NULL; counts without labels, or with
+ * label_rows <= 0 or n % label_rows != 0; x or a weight NULL with n > 0. */
+int mvk_polyclf_tile(void);
+int mvk_polyclf_fwd(const float* x, int64_t n, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                    const float* b3, const float* w4, const float* b4, float* logits, int32_t* pred, const int64_t* labels,
+                    int64_t label_rows, int64_t* counts, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

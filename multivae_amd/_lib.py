@@ -241,6 +241,8 @@ PROTOTYPES = {
     "mvk_fd_begin": [_p, _p, _i64, _i, _p, _p],
     "mvk_fd_update": [_p, _p, _i64, _i, _p, _p],
     "mvk_fd_finish": [_p, _i, _p, _p, _p, _p],
+    "mvk_polyclf_tile": [],  # returns the images per workgroup, not a status
+    "mvk_polyclf_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p],
 }
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8

@@ -2900,6 +2900,50 @@ def fd_finish(state, D, mean=None, cov=None, terms=None):
 
 
 # =====================================================================================================
+# PolyMNIST classifier (metrics.classifiers.ClassifierPolyMNIST, metrics.CoherenceEvaluator)
+# =====================================================================================================
+POLYCLF_SHAPES = ((10, 3, 4, 4), (10,), (20, 10, 4, 4), (20,), (128, 980), (128,), (10, 128), (10,))
+
+
+def polyclf_tile():
+    """Images per workgroup of the fused classifier launch (mvk_polyclf_tile)."""
+    return _lib.load().mvk_polyclf_tile()
+
+
+def polyclf_forward(x, params, logits=None, pred=None, labels=None, counts=None):
+    """The PolyMNIST classifier in eval mode on x [n,3,28,28] fp32 in one launch (mvk_polyclf_fwd).  params: the eight parameters
+    (conv1 w, b, conv2 w, b, fc1 w, b, fc2 w, b) in PyTorch's layouts, read in place.  Outputs, each optional: logits [n,10] fp32,
+    pred [n] int32 (torch.argmax), counts [11,2] int64 += the (correct, count) pairs of ClassCounts.update under
+    labels[i % len(labels)] (int64).  With no output given, logits are allocated and returned."""
+    _lib.require_gpu_tensor(x, "x")
+    if x.dim() != 4 or tuple(x.shape[1:]) != (3, 28, 28) or not x.is_contiguous():
+        raise ValueError(f"polyclf_forward: x must be a contiguous [n,3,28,28] tensor, got {tuple(x.shape)}")
+    if len(params) != 8:
+        raise ValueError("polyclf_forward: eight parameters (conv1, conv2, fc1, fc2: weight and bias)")
+    for p, shape in zip(params, POLYCLF_SHAPES):
+        _lib.require_gpu_tensor(p, "a classifier parameter")
+        if tuple(p.shape) != shape or not p.is_contiguous() or p.device != x.device:
+            raise ValueError(f"polyclf_forward: a contiguous parameter of shape {shape} on {x.device}, got {tuple(p.shape)} on {p.device}")
+    n = x.shape[0]
+    if logits is None and pred is None and counts is None:
+        logits = torch.empty(n, 10, dtype=torch.float32, device=x.device)
+    for t, name, dtype, shape in ((logits, "logits", torch.float32, (n, 10)), (pred, "pred", torch.int32, (n,)),
+                                  (counts, "counts", torch.int64, (11, 2))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device):
+            raise ValueError(f"polyclf_forward: {name} must be a contiguous {dtype} tensor of shape {shape} on {x.device}")
+    label_rows = 0
+    if labels is not None:
+        if labels.dtype != torch.int64 or labels.dim() != 1 or not labels.is_contiguous() or labels.device != x.device:
+            raise ValueError(f"polyclf_forward: labels must be a contiguous 1-d int64 tensor on {x.device}")
+        label_rows = labels.shape[0]
+    if n == 0:  # nothing to classify (an empty tensor has no address to hand over)
+        return logits
+    call("mvk_polyclf_fwd", ptr(x), n, *[ptr(p) for p in params], ptr(logits), ptr(pred), ptr(labels), label_rows, ptr(counts),
+         stream_ptr())
+    return logits
+
+
+# =====================================================================================================
 # Masked autoregressive flows (models/nn/flows.py; JNF)
 # =====================================================================================================
 def maf_fused_ok(D, H, n_hidden, n_blocks, M=1):

@@ -2,8 +2,11 @@
 
 The reference keeps one torchmetrics `MulticlassAccuracy(num_classes, average=None)` per generated modality.  Its per-class accuracy
 is fixed here from the definition (torchmetrics was not at hand): correct_c / count_c over everything accumulated, c being the
-TRUE class, and 0 for a class that never occurs.  The counts are [num_classes, 2] integers on the device, updated with
-torch ops (the classifiers are user modules: there is nothing here for a kernel), and read once per subset."""
+TRUE class, and 0 for a class that never occurs.  The counts are [num_classes + 1, 2] integers on the device, read once per
+subset.  A classifier is a user module in general, and then the counts are updated with torch ops on its logits; where it is
+exactly a `ClassifierPolyMNIST` (num_classes = 10, CUDA fp32 [n,3,28,28] generations) the fused launch of csrc/clf.hip classifies
+the batch and adds straight into the counts (cross coherences) or writes the argmax (joint coherence): one launch per generated
+modality and batch, no logits tensor.  Both paths give the same counts."""
 from itertools import combinations
 from typing import Dict, List, Optional
 
@@ -13,6 +16,7 @@ import torch
 from ..._output import ModelOutput
 from ...data.utils import set_inputs_to_device
 from ..base.evaluator_class import Evaluator
+from ..classifiers.mmnist import ClassifierPolyMNIST
 from .coherences_config import CoherenceEvaluatorConfig
 
 
@@ -60,6 +64,13 @@ class CoherenceEvaluator(Evaluator):
         for k in self.clfs:
             self.clfs[k] = self.clfs[k].to(self.device).eval()
 
+    def _fused(self, m, x):
+        """The modality's classifier when the fused launch can classify x, else None (the general path)."""
+        clf = self.clfs[m]
+        if type(clf) is ClassifierPolyMNIST and self.num_classes == 10 and clf.kernel_ok(x):
+            return clf
+        return None
+
     def cross_coherences(self):
         """Every coherence from a subset of the modalities to another modality; returns the means and standard deviations over
         the subsets of each size."""
@@ -104,8 +115,15 @@ class CoherenceEvaluator(Evaluator):
                 labels = batch.labels
                 if self.nb_samples_for_cross > 1:  # the generations are stacked sample-major: [N * batch, ...]
                     labels = torch.stack([labels] * self.nb_samples_for_cross, dim=0).reshape(-1, *labels.shape[1:])
+                flat_labels = None
                 for pred_m in pred_mods:
-                    counts[pred_m].update(self.clfs[pred_m](output[pred_m]), labels)
+                    clf = self._fused(pred_m, output[pred_m])
+                    if clf is None:
+                        counts[pred_m].update(self.clfs[pred_m](output[pred_m]), labels)
+                        continue
+                    if flat_labels is None:  # the kernel stacks the batch's labels itself: row i has labels[i % rows]
+                        flat_labels = batch.labels.to(self.device).long().reshape(-1).contiguous()
+                    clf.classify(output[pred_m], labels=flat_labels, counts=counts[pred_m].counts)
         acc_per_class = {f"{subset_name}_to_{m}": counts[m].compute().cpu() for m in counts}
         acc = {m: acc_per_class[m].mean() for m in acc_per_class}
         self.logger.info("Subset %s accuracies ", subset)
@@ -135,7 +153,13 @@ class CoherenceEvaluator(Evaluator):
                     output_prior.modalities_z[m] = output_prior.modalities_z[m].to(self.device).reshape(batch_samples, -1)
             output_decode = self.model.decode(output_prior)
             with torch.no_grad():
-                labels = [torch.argmax(self.clfs[m](output_decode[m]), dim=1) for m in output_decode.keys()]
+                labels = []
+                for m in output_decode.keys():
+                    clf = self._fused(m, output_decode[m])
+                    if clf is None:
+                        labels.append(torch.argmax(self.clfs[m](output_decode[m]), dim=1))
+                    else:
+                        labels.append(clf.classify(output_decode[m]).long())
             same += torch.all(torch.stack([l == labels[0] for l in labels]), dim=0).sum()
             samples_to_generate -= batch_samples
         joint_coherence = same.float() / self.nb_samples_for_joint
