@@ -1210,6 +1210,60 @@ int mvk_polyclf_fwd(const float* x, int64_t n, const float* w1, const float* b1,
                     const float* b3, const float* w4, const float* b4, float* logits, int32_t* pred, const int64_t* labels,
                     int64_t label_rows, int64_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * CUB text encoder (models/nn/cub.py CubTextEncoder): the stages of a post-norm transformer encoder over short sentences
+ * that are not GEMMs (csrc/textenc.hip).  tokens [B,S] int64; activations [B,S,E] fp32; the packed in-projection
+ * qkv [B,S,3E] (q | k | v, head h owning columns h*hd .. h*hd + hd - 1 of each third, hd = E / nhead).
+ *
+ * Dropout.  Every site reads uniform noise u in [0,1) from a caller-owned buffer: an element is kept iff u >= p and then
+ * scaled by 1 / (1 - p); the backward entries re-read the same noise (no mask is stored).  noise == NULL or p == 0: no
+ * dropout.  0 <= p < 1.  One forward's noise is ONE flat buffer, the sites in this order (floats):
+ *   pos [B,S,E], then per layer: attn [B,nhead,S,S], res1 [B,S,E], ff [B,S,F], res2 [B,S,E];
+ * every entry takes the pointer of its own site.
+ *
+ * Every sum runs in a fixed order and there is no floating-point atomic: results are bit-identical from run to run.
+ * Optional pointers may be NULL.  MVK_EINVAL: a required pointer NULL, a size < 1, p outside [0,1), and what each entry
+ * names. */
+/* out[b,s,:] = drop(emb[tokens[b,s],:] * sqrt(E) + pe[s,:]); emb [V,E], pe [>= S,E].  A token outside [0,V) reads no
+ * embedding row (its embedding counts as 0). */
+int mvk_txt_embed_fwd(const int64_t* tokens, const float* emb, const float* pe, const float* noise, float p, float* out,
+                      int B, int S, int E, int V, void* stream);
+/* dE[v,:] (+= when accumulate != 0, else =) sqrt(E) * sum over (b,s) with tokens[b,s] == v of keep * scale * (g + g2)[b,s,:],
+ * the rows that share a token added in (b,s) order; a row no token names gets 0 (accumulate == 0) or stays.  g2 (the
+ * second gradient of the residual stream) may be NULL. */
+int mvk_txt_embed_bwd(const int64_t* tokens, const float* g, const float* g2, const float* noise, float p, float* dE,
+                      int accumulate, int B, int S, int E, int V, void* stream);
+/* One workgroup per (sentence, head): scores = (q / sqrt(hd)) k^T, keys with keymask[b,j] == 0 at -inf (keymask int32
+ * [B,S], NULL = every key real), P = softmax over j, ctx[b,i,h*hd + d] = sum_j drop(P)[i,j] v[j,d].  P [B,nhead,S,S]
+ * receives the probabilities BEFORE dropout (NULL: not kept).  A sentence with no real key gives NaN, like torch.
+ * 1 <= S <= MVK_TXT_MAX_SEQ, E % nhead == 0, hd <= MVK_TXT_MAX_HEAD_DIM. */
+#define MVK_TXT_MAX_SEQ 64
+#define MVK_TXT_MAX_HEAD_DIM 128
+int mvk_txt_attn_fwd(const float* qkv, const int32_t* keymask, const float* noise, float p, float* P, float* ctx,
+                     int B, int S, int E, int nhead, void* stream);
+/* dqkv [B,S,3E] from dctx [B,S,E], with D = keep * scale of the attention site:  dV = (P o D)^T dctx,
+ * dP = (dctx V^T) o D, dS = P o (dP - rowsum(dP o P)), dQ = dS K / sqrt(hd), dK = dS^T Q / sqrt(hd).  Same limits. */
+int mvk_txt_attn_bwd(const float* qkv, const float* P, const float* dctx, const float* noise, float p, float* dqkv,
+                     int B, int S, int E, int nhead, void* stream);
+/* z = x + drop(t), y = (z - mean) * rstd * gamma + beta over the E entries of each of `rows` rows (biased variance,
+ * rstd = 1 / sqrt(var + eps)).  gamma / beta NULL: 1 / 0.  z [rows,E] (may be NULL, may alias t), mean, rstd [rows] (may
+ * be NULL) are what the backward reads.  zero_pads != 0 with rowmask (int32 [rows], 0 = padded): y = 0 on padded rows
+ * (the last layer of an evaluation forward).  y must not alias x or t. */
+int mvk_txt_add_ln_fwd(const float* x, const float* t, const float* noise, float p, const float* gamma, const float* beta,
+                       float eps, const int32_t* rowmask, int zero_pads, float* y, float* z, float* mean, float* rstd,
+                       int64_t rows, int E, void* stream);
+/* With g = (dy + dy2) * gamma and xh = (z - mean) * rstd:  dx = rstd * (g - mean_e(g) - xh * mean_e(g * xh)) (the residual
+ * stream), dt = keep * scale * dx (through the dropout; NULL: not wanted — without dropout dt == dx),
+ * dgamma[e] += sum_r (dy + dy2) * xh, dbeta[e] += sum_r (dy + dy2): column sums in two stages, slabs of 64 rows into ws
+ * (needs 2 * E * ceil(rows / 64) floats, MVK_EINVAL below that) and then over the slabs in order.  dy2, dt, dgamma, dbeta
+ * may be NULL (ws too when both sums are). */
+int mvk_txt_add_ln_bwd(const float* dy, const float* dy2, const float* z, const float* mean, const float* rstd,
+                       const float* gamma, const float* noise, float p, float* dx, float* dt, float* dgamma, float* dbeta,
+                       float* ws, int64_t ws_floats, int64_t rows, int E, void* stream);
+/* x = keep * scale * x in place over n floats: the feed-forward dropout, forward (on relu(W1 h + b1)) and backward (on the
+ * gradient of that product) alike. */
+int mvk_txt_drop(float* x, const float* noise, float p, int64_t n, void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -243,7 +243,15 @@ PROTOTYPES = {
     "mvk_fd_finish": [_p, _i, _p, _p, _p, _p],
     "mvk_polyclf_tile": [],  # returns the images per workgroup, not a status
     "mvk_polyclf_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p],
+    "mvk_txt_embed_fwd": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _p],
+    "mvk_txt_embed_bwd": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _p],
+    "mvk_txt_attn_fwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p],
+    "mvk_txt_attn_bwd": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _p],
+    "mvk_txt_add_ln_fwd": [_p, _p, _p, _f, _p, _p, _f, _p, _i, _p, _p, _p, _p, _i64, _i, _p],
+    "mvk_txt_add_ln_bwd": [_p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i64, _i64, _i, _p],
+    "mvk_txt_drop": [_p, _p, _f, _i64, _p],
 }
+TXT_MAX_SEQ, TXT_MAX_HEAD_DIM = 64, 128  # MVK_TXT_MAX_SEQ / MVK_TXT_MAX_HEAD_DIM
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8
 SSIM_ACC = {"ssim": 0, "sse": 1, "rows": 2}  # MVK_SSIM_ACC_* (a block of 3 doubles)

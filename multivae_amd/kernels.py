@@ -3173,3 +3173,196 @@ class IAFFlowFn(Function):
                           None if dz0 is None else _c(dz0), None if dladj is None else _c(dladj), want_dx=need[1],
                           dWs=targets[0::2], dbs=targets[1::2])
         return (None, dx, *rets)
+
+
+# =====================================================================================================
+# CUB text encoder  (models/nn/cub.py CubTextEncoder; csrc/textenc.hip, include/mvk.h "CUB text encoder")
+# =====================================================================================================
+def text_encoder_ok(B, S, E, nhead, F):
+    """Whether the fused text-encoder path covers this shape (mvk_txt_attn_*: S <= 64, head_dim <= 128)."""
+    return bool(B >= 1 and 1 <= S <= _lib.TXT_MAX_SEQ and nhead >= 1 and E >= nhead and E % nhead == 0
+                and E // nhead <= _lib.TXT_MAX_HEAD_DIM and F >= 1)
+
+
+def text_noise_layout(B, S, E, nhead, F, n_layers):
+    """(floats of one forward's dropout noise, offset of the positional site, [(attn, res1, ff, res2) offsets per layer]):
+    pos [B,S,E], then per layer attn [B,nhead,S,S], res1 [B,S,E], ff [B,S,F], res2 [B,S,E] (include/mvk.h)."""
+    off, layers = B * S * E, []
+    for _ in range(n_layers):
+        a = off
+        r1 = a + B * nhead * S * S
+        f = r1 + B * S * E
+        r2 = f + B * S * F
+        off = r2 + B * S * E
+        layers.append((a, r1, f, r2))
+    return off, 0, layers
+
+
+def _txt_site(noise, off, n, p):
+    """The noise of one dropout site (None: no dropout there)."""
+    return None if noise is None or p == 0 else noise[off:off + n]
+
+
+def txt_embed_fwd(tokens, emb, pe, noise=None, p=0.0):
+    """drop(emb[tokens] * sqrt(E) + pe[:S]) -> [B,S,E] (mvk_txt_embed_fwd).  tokens int64 [B,S]; pe [>= S,E]."""
+    B, S = tokens.shape
+    V, E = emb.shape
+    out = _new((B, S, E), emb)
+    call("mvk_txt_embed_fwd", ptr(tokens), ptr(emb), ptr(pe), ptr(noise), float(p), ptr(out), B, S, E, V, stream_ptr())
+    return out
+
+
+def txt_embed_bwd(tokens, g, V, g2=None, noise=None, p=0.0, out=None):
+    """The embedding table's gradient [V,E] (mvk_txt_embed_bwd); out: a buffer to accumulate into."""
+    B, S = tokens.shape
+    E = g.shape[-1]
+    dE = out if out is not None else _new((V, E), g)
+    call("mvk_txt_embed_bwd", ptr(tokens), ptr(g), ptr(g2), ptr(noise), float(p), ptr(dE), 1 if out is not None else 0, B, S, E, V,
+         stream_ptr())
+    return dE
+
+
+def txt_attn_fwd(qkv, nhead, keymask=None, noise=None, p=0.0, keep=True):
+    """Masked self-attention of every (sentence, head) from the packed qkv [B,S,3E] -> (ctx [B,S,E], P [B,nhead,S,S] before
+    dropout, or None) (mvk_txt_attn_fwd).  keymask int32 [B,S], 1 = real key."""
+    B, S, E3 = qkv.shape
+    E = E3 // 3
+    ctx = _new((B, S, E), qkv)
+    P = _new((B, nhead, S, S), qkv) if keep else None
+    call("mvk_txt_attn_fwd", ptr(qkv), ptr(keymask), ptr(noise), float(p), ptr(P), ptr(ctx), B, S, E, nhead, stream_ptr())
+    return ctx, P
+
+
+def txt_attn_bwd(qkv, P, dctx, nhead, noise=None, p=0.0):
+    """dqkv [B,S,3E] (mvk_txt_attn_bwd)."""
+    B, S, E3 = qkv.shape
+    dqkv = _new((B, S, E3), qkv)
+    call("mvk_txt_attn_bwd", ptr(qkv), ptr(P), ptr(dctx), ptr(noise), float(p), ptr(dqkv), B, S, E3 // 3, nhead, stream_ptr())
+    return dqkv
+
+
+def txt_add_ln_fwd(x, t, gamma, beta, eps, noise=None, p=0.0, rowmask=None, zero_pads=False, keep=True, z_in_t=False):
+    """y = LN(x + drop(t)) gamma + beta over the last axis -> (y, z, mean, rstd) (mvk_txt_add_ln_fwd); z, mean, rstd are None
+    without keep; z_in_t: z overwrites t."""
+    E = x.shape[-1]
+    rows = x.numel() // E
+    y = _new(x.shape, x)
+    z = (t if z_in_t else _new(x.shape, x)) if keep else None
+    mean = _new((rows,), x) if keep else None
+    rstd = _new((rows,), x) if keep else None
+    call("mvk_txt_add_ln_fwd", ptr(x), ptr(t), ptr(noise), float(p), ptr(gamma), ptr(beta), float(eps), ptr(rowmask),
+         1 if zero_pads else 0, ptr(y), ptr(z), ptr(mean), ptr(rstd), rows, E, stream_ptr())
+    return y, z, mean, rstd
+
+
+def txt_add_ln_bwd(dy, z, mean, rstd, gamma, dy2=None, noise=None, p=0.0, want_dt=True, dgamma=None, dbeta=None):
+    """-> (dx, dt) of y = LN(x + drop(t)) gamma + beta for the upstream gradient dy + dy2; dgamma / dbeta (buffers or None)
+    are accumulated into (mvk_txt_add_ln_bwd).  Without dropout dt is dx itself."""
+    E = dy.shape[-1]
+    rows = dy.numel() // E
+    dx = _new(dy.shape, dy)
+    dropped = noise is not None and p > 0
+    dt = _new(dy.shape, dy) if want_dt and dropped else None
+    ws = _new((2 * E * ((rows + 63) // 64),), dy) if dgamma is not None or dbeta is not None else None
+    call("mvk_txt_add_ln_bwd", ptr(dy), ptr(dy2), ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(noise), float(p), ptr(dx), ptr(dt),
+         ptr(dgamma), ptr(dbeta), ptr(ws), 0 if ws is None else ws.numel(), rows, E, stream_ptr())
+    return dx, (dt if dropped or not want_dt else dx)
+
+
+def txt_drop(x, noise=None, p=0.0):
+    """x = keep * x / (1 - p) in place (mvk_txt_drop)."""
+    call("mvk_txt_drop", ptr(x), ptr(noise), float(p), x.numel(), stream_ptr())
+    return x
+
+
+TXT_LAYER_PARAMS = 12  # in_proj w, b; out_proj w, b; linear1 w, b; linear2 w, b; norm1 w, b; norm2 w, b
+
+
+class TextEncoderFn(Function):
+    """tokens -> embedding + positions -> n post-norm transformer encoder layers -> [B,S,E], one node.
+    apply(tokens, padding_mask, p, noise, zero_pads, nhead, eps, emb, pe, *layer params): tokens int64 [B,S]; padding_mask [B,S]
+    (non-zero = real token) or None; p the dropout rate and noise the flat U[0,1) buffer of text_noise_layout (None: no dropout);
+    zero_pads: the output is 0 at padded positions (evaluation without autograd only); eps the LayerNorm epsilon; emb [V,E];
+    pe [>= S,E]; then TXT_LAYER_PARAMS parameters per layer.  The five GEMM sites of a layer are the tiled engine's, the other
+    stages csrc/textenc.hip; the backward re-reads the noise and keeps no mask."""
+
+    @staticmethod
+    def forward(ctx, tokens, padding_mask, p, noise, zero_pads, nhead, eps, emb, pe, *params):
+        n_layers = len(params) // TXT_LAYER_PARAMS
+        B, S = tokens.shape
+        V, E = emb.shape
+        F = params[4].shape[0]
+        if not text_encoder_ok(B, S, E, nhead, F) or len(params) != n_layers * TXT_LAYER_PARAMS:
+            raise _lib.MvkError(f"TextEncoderFn: shape B={B} S={S} E={E} nhead={nhead} F={F} is not covered")
+        _lib.require_gpu_tensor(emb, "emb")
+        p = float(p)
+        if noise is None or p == 0:
+            noise, p = None, 0.0
+        keep = any(ctx.needs_input_grad) and not zero_pads  # zero_pads: evaluation without autograd, nothing is kept
+        total, pos_off, offs = text_noise_layout(B, S, E, nhead, F, n_layers)
+        if noise is not None and (noise.numel() < total or noise.dtype != torch.float32 or not noise.is_contiguous()):
+            raise _lib.MvkError(f"TextEncoderFn: noise must be a contiguous float32 buffer of {total} entries")
+        tokens = tokens.contiguous()
+        keymask = None if padding_mask is None else (padding_mask != 0).to(torch.int32).contiguous()
+        M = B * S
+        h = txt_embed_fwd(tokens, emb, pe, _txt_site(noise, pos_off, M * E, p), p).view(M, E)
+        acts = []
+        for l in range(n_layers):
+            w_in, b_in, w_o, b_o, w1, b1, w2, b2, g1, be1, g2, be2 = params[l * TXT_LAYER_PARAMS:(l + 1) * TXT_LAYER_PARAMS]
+            oa, or1, of, or2 = offs[l]
+            qkv = linear_fwd(h, w_in, b_in, NONE)
+            cx, P = txt_attn_fwd(qkv.view(B, S, 3 * E), nhead, keymask, _txt_site(noise, oa, B * nhead * S * S, p), p, keep=keep)
+            cx = cx.view(M, E)
+            a = linear_fwd(cx, w_o, b_o, NONE)
+            y1, z1, m1, r1 = txt_add_ln_fwd(h, a, g1, be1, eps, _txt_site(noise, or1, M * E, p), p, keep=keep, z_in_t=True)
+            f1 = txt_drop(linear_fwd(y1, w1, b1, RELU), _txt_site(noise, of, M * F, p), p)
+            f2 = linear_fwd(f1, w2, b2, NONE)
+            last = l == n_layers - 1
+            y2, z2, m2, r2 = txt_add_ln_fwd(y1, f2, g2, be2, eps, _txt_site(noise, or2, M * E, p), p,
+                                            rowmask=keymask if last and zero_pads else None, zero_pads=last and zero_pads,
+                                            keep=keep, z_in_t=True)
+            if keep:
+                acts += [h, qkv, P, cx, z1, m1, r1, y1, f1, z2, m2, r2]
+            h = y2
+        if keep:
+            ctx.save_for_backward(tokens, noise, emb, *params, *acts)
+        ctx.cfg = (B, S, E, F, V, nhead, n_layers, p)
+        return h.view(B, S, E)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        B, S, E, F, V, nhead, n_layers, p = ctx.cfg
+        saved = ctx.saved_tensors
+        tokens, noise, emb = saved[:3]
+        params = saved[3:3 + n_layers * TXT_LAYER_PARAMS]
+        acts = saved[3 + n_layers * TXT_LAYER_PARAMS:]
+        M = B * S
+        _, pos_off, offs = text_noise_layout(B, S, E, nhead, F, n_layers)
+        grads = [None] * len(params)
+        dy, dy2 = _c(dout).view(M, E), None
+        for l in range(n_layers - 1, -1, -1):
+            w_in, b_in, w_o, b_o, w1, b1, w2, b2, g1, be1, g2, be2 = params[l * TXT_LAYER_PARAMS:(l + 1) * TXT_LAYER_PARAMS]
+            h, qkv, P, cx, z1, m1, r1, y1, f1, z2, m2, r2 = acts[12 * l:12 * (l + 1)]
+            oa, or1, of, or2 = offs[l]
+            k = l * TXT_LAYER_PARAMS
+            (tg2, grads[k + 10]), (tb2, grads[k + 11]) = _grad_target(g2), _grad_target(be2)
+            dx2, dt2 = txt_add_ln_bwd(dy, z2, m2, r2, g2, dy2, _txt_site(noise, or2, M * E, p), p, dgamma=tg2, dbeta=tb2)
+            grads[k + 6], grads[k + 7] = linear_bwd_weight(dt2, f1, w2, b2)
+            # f1 is what linear2 read: relu(.) after the dropout, zero where dropped — its ReLU' carries the mask, the scale follows
+            df1 = txt_drop(linear_bwd_data(dt2, w2, prev_out=f1, prev_act=RELU), _txt_site(noise, of, M * F, p), p)
+            grads[k + 4], grads[k + 5] = linear_bwd_weight(df1, y1, w1, b1)
+            dy1 = linear_bwd_data(df1, w1)
+            (tg1, grads[k + 8]), (tb1, grads[k + 9]) = _grad_target(g1), _grad_target(be1)
+            dx1, dt1 = txt_add_ln_bwd(dx2, z1, m1, r1, g1, dy1, _txt_site(noise, or1, M * E, p), p, dgamma=tg1, dbeta=tb1)
+            grads[k + 2], grads[k + 3] = linear_bwd_weight(dt1, cx, w_o, b_o)
+            dcx = linear_bwd_data(dt1, w_o)
+            dqkv = txt_attn_bwd(qkv.view(B, S, 3 * E), P, dcx.view(B, S, E), nhead, _txt_site(noise, oa, B * nhead * S * S, p), p)
+            dqkv = dqkv.view(M, 3 * E)
+            grads[k], grads[k + 1] = linear_bwd_weight(dqkv, h, w_in, b_in)
+            dy, dy2 = dx1, linear_bwd_data(dqkv, w_in)
+        gemb = None
+        if ctx.needs_input_grad[7]:
+            te, gemb = _grad_target(emb)
+            txt_embed_bwd(tokens, dy, V, dy2, _txt_site(noise, pos_off, M * E, p), p, out=te)
+        return (None, None, None, None, None, None, None, gemb, None, *grads)

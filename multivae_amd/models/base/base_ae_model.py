@@ -19,6 +19,14 @@ from .base_model import BaseModel
 from .base_utils import ModelOutput, decoder_dist_code
 
 
+def first_tensor(entry):
+    """A modality's batch entry is a tensor or, for a text modality, the reference's dict of tensors ("tokens", "padding_mask",
+    optionally "one_hot"): the tensor that tells the batch size, the device and the shape."""
+    if isinstance(entry, dict):
+        return entry["tokens"] if "tokens" in entry else next(iter(entry.values()))
+    return entry
+
+
 class BaseMultiVAE(BaseModel):
     def __init__(self, model_config: BaseMultiVAEConfig, encoders: dict = None, decoders: dict = None):
         super().__init__(model_config)
@@ -67,7 +75,7 @@ class BaseMultiVAE(BaseModel):
         def size(m):
             d = dims.get(m)
             if d is None and inputs is not None and m in inputs.data:
-                d = tuple(inputs.data[m].shape[1:])
+                d = tuple(first_tensor(inputs.data[m]).shape[1:])
             n = 1
             for v in (d or ()):
                 n *= int(v)
@@ -303,10 +311,18 @@ class BaseMultiVAE(BaseModel):
             return torch.empty(shape, device=device, dtype=torch.float32).uniform_(lo, 1.0)
         return torch.randn(shape, device=device, dtype=torch.float32)
 
-    def _recon_spec(self, names, data, masks, K, B):
+    def _recon_spec(self, names, data, masks, K, B, recons=None):
+        """recons: the decoders' outputs in the order of `names`; a text dict's tokens become a one-hot target with their class
+        count (without them: the last entry of input_dims)."""
         xs, mks, dist, scale, resc = [], [], [], [], []
-        for m in names:
+        for i, m in enumerate(names):
             x = data[m]
+            if isinstance(x, dict):  # the float target of the categorical kernel, built once per batch
+                if "one_hot" in x:
+                    x = x["one_hot"]
+                else:
+                    n_classes = recons[i].shape[-1] if recons is not None else int(self.input_dims[m][-1])
+                    x = torch.nn.functional.one_hot(x["tokens"], n_classes)
             if x.dtype != torch.float32:
                 x = x.float()
             xs.append(x.contiguous())

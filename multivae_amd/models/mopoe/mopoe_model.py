@@ -14,6 +14,7 @@ import torch
 
 from ... import kernels, schedule
 from ..base import BaseMultiVAE
+from ..base.base_ae_model import first_tensor
 from ..base.base_utils import ModelOutput
 from .mopoe_config import MoPoEConfig
 
@@ -126,12 +127,12 @@ class MoPoE(BaseMultiVAE):
                 side_work()  # BEHIND the short encoder: its stream also carries the step's weight-pack launch (kernels.pack_scope)
             return out
 
-        enc = schedule.run_branches(names, run, inputs.data[names[0]].device)
+        enc = schedule.run_branches(names, run, first_tensor(inputs.data[names[0]]).device)
         return {m: enc[m] for m in self.encoders.keys()}
 
     def _posterior(self, inputs, K, noise=None, choice=None, want_stats=False):
         early = {}
-        x0 = next(iter(inputs.data.values()))
+        x0 = first_tensor(next(iter(inputs.data.values())))
         if noise is None and x0.is_cuda and schedule.BRANCH_STREAMS and len(self.encoders) > 1 \
                 and x0.dim() > 1:
             # the noise does not depend on the encoders: its launch rides at the head of the short encoder's branch stream
@@ -228,7 +229,7 @@ class MoPoE(BaseMultiVAE):
         plain = [m for m in names if rec[m][0] == "rec"]
         fused = [m for m in names if rec[m][0] == "rows"]
         recons = [rec[m][1] for m in plain]
-        spec = self._recon_spec(plain, inputs.data, masks, K, B)
+        spec = self._recon_spec(plain, inputs.data, masks, K, B, recons)
         M, S, Fz = len(plain), len(style_kl), len(fused)
         beta = float(self.model_config.beta)
         spec.update(coef=[1.0 / (K * B)] * M, lossw=[1.0] * M,

@@ -109,6 +109,13 @@ class _BatchIterator:
             if getattr(base, "labels", None) is not None and torch.is_tensor(base.labels):
                 self.labels = base.labels.to(device)
 
+    def _collate(self, vals):
+        """One modality of a batch from its per-sample items: tensors are stacked; a text modality's dict of tensors (the
+        reference's CUB captions: "tokens", "padding_mask", "one_hot") is stacked entry by entry."""
+        if isinstance(vals[0], dict):
+            return {k: self._collate([v[k] for v in vals]) for k in vals[0]}
+        return torch.stack([torch.as_tensor(v) for v in vals]).to(self.device)
+
     def __len__(self):
         n = self._n_local()
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size
@@ -150,8 +157,7 @@ class _BatchIterator:
                 yield DatasetOutput(**out)
             else:  # generic datasets: per-sample items, collated here
                 items = [self.dataset[int(i)] for i in idx]
-                out = {"data": {m: torch.stack([torch.as_tensor(it["data"][m]) for it in items]).to(self.device)
-                                for m in items[0]["data"]}}
+                out = {"data": {m: self._collate([it["data"][m] for it in items]) for m in items[0]["data"]}}
                 if "masks" in items[0]:
                     out["masks"] = {m: torch.stack([torch.as_tensor(it["masks"][m]) for it in items]).to(self.device)
                                     for m in items[0]["masks"]}
@@ -364,6 +370,8 @@ class BaseTrainer:
         if not (self.training_config.use_hip_graph and isinstance(self.optimizer, FusedAdam)
                 and self.device.type == "cuda" and not hasattr(inputs, "masks")):
             return None
+        if any(isinstance(v, dict) for v in inputs.data.values()):
+            return None  # a text modality's dict entry: the captured step stages tensor entries only, such a batch runs eagerly
         from ..graph import GraphedStep
 
         cfg = self.training_config
