@@ -1264,6 +1264,41 @@ int mvk_txt_add_ln_bwd(const float* dy, const float* dy2, const float* z, const 
  * gradient of that product) alike. */
 int mvk_txt_drop(float* x, const float* noise, float p, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The image grid of a set of modality tensors (metrics.Visualization, BaseTrainer.predict)
+ * ------------------------------------------------------------------------------------------------ */
+/* data/datasets/utils.py:50-91 (adapt_shape) -> torch.cat -> torchvision.utils.make_grid(nrow, padding, pad_value;
+ * normalize=False) -> mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(uint8) (metrics/visualization/
+ * visualization_class.py:93-108, trainers/base/base_trainer.py:830-917) in one launch that writes every element of its
+ * outputs exactly once (no memset in front, no atomics).
+ *   srcs   HOST array of S <= MVK_GRID_MAX_SOURCES descriptors, copied into the launch: `data` a device tensor
+ *          [n, c, h, w] of contiguous fp32.  The tiles are the images of source 0, then of source 1, ...: T = sum n.
+ *          A source with n == 0 adds no tile and does not count towards the tile size (its data may be NULL).
+ *   channels  c == 1: replicated to three; c == 2: the third channel is 0; c >= 3: the first three.
+ *   centring  H = max h, W = max w over the sources.  An image sits in its H x W tile behind floor((H - h) / 2) rows and
+ *          floor((W - w) / 2) columns of zeros (the ceil of each follows it).  These zeros are part of the tile: 0,
+ *          not pad_value.
+ *   grid   xmaps = min(nrow, T), ymaps = ceil(T / xmaps), Hg = ymaps (H + padding) + padding, Wg = xmaps (W + padding)
+ *          + padding; tile k has its corner at row (k / xmaps) (H + padding) + padding, column (k % xmaps) (W + padding)
+ *          + padding; every other pixel, the empty cells of a last row included, is pad_value.  T == 1 is make_grid's
+ *          exception: the single image without a border, Hg = H, Wg = W.
+ * outputs (either may be NULL)
+ *   grid   [3, Hg, Wg] fp32 (any 4-byte aligned address): copies of the inputs, bit for bit
+ *   image  [Hg, Wg, 3] uint8 (any address): (uint8) clamp(fl(fl(255 x) + 0.5), 0, 255), the product rounded to fp32 before
+ *          the sum is (never an fma); +inf gives 255, -inf 0, and a NaN gives 0.
+ * MVK_EINVAL: S > MVK_GRID_MAX_SOURCES, nrow <= 0, padding < 0, a negative n, a non-positive c, h or w, 3 Hg Wg >= 2^31
+ * (all decided from the descriptors' shapes, before `data` is looked at and before any launch), a NULL `data` of a
+ * source with images.  T == 0 is a no-op that returns MVK_OK.  mvk_image_grid_size reports T, Hg and Wg (0, 0, 0 for
+ * T == 0) under the same refusals and reads no `data`. */
+#define MVK_GRID_MAX_SOURCES 32
+typedef struct {
+  const float* data;
+  int32_t n, c, h, w;
+} mvk_grid_src;
+int mvk_image_grid_size(const mvk_grid_src* srcs, int S, int nrow, int padding, int64_t* T, int64_t* Hg, int64_t* Wg);
+int mvk_image_grid(const mvk_grid_src* srcs, int S, int nrow, int padding, float pad_value, float* grid, uint8_t* image,
+                   void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -74,6 +74,10 @@ class SeedDesc(C.Structure):  # mvk_seed_desc
     _fields_ = [("buf", _p), ("n", _i64), ("coef", _f), ("fill", C.c_int32)]
 
 
+class GridSrc(C.Structure):  # mvk_grid_src
+    _fields_ = [("data", _p), ("n", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32)]
+
+
 class TermDesc(C.Structure):
     _fields_ = [("v", _p), ("mask", _p), ("n", _i64), ("period", _i64), ("coef", _f), ("lossw", _f), ("gfill", _p)]
 
@@ -250,7 +254,10 @@ PROTOTYPES = {
     "mvk_txt_add_ln_fwd": [_p, _p, _p, _f, _p, _p, _f, _p, _i, _p, _p, _p, _p, _i64, _i, _p],
     "mvk_txt_add_ln_bwd": [_p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i64, _i64, _i, _p],
     "mvk_txt_drop": [_p, _p, _f, _i64, _p],
+    "mvk_image_grid_size": [C.POINTER(GridSrc), _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "mvk_image_grid": [C.POINTER(GridSrc), _i, _i, _i, _f, _p, _p, _p],
 }
+GRID_MAX_SOURCES = 32  # MVK_GRID_MAX_SOURCES
 TXT_MAX_SEQ, TXT_MAX_HEAD_DIM = 64, 128  # MVK_TXT_MAX_SEQ / MVK_TXT_MAX_HEAD_DIM
 GMM_STATE = {"iter": 0, "prev": 1, "lb": 2, "converged": 3, "status": 4, "pending": 5}  # MVK_GMM_STATE_* (a block of 8 doubles)
 GMM_STATE_DOUBLES = 8

@@ -3366,3 +3366,94 @@ class TextEncoderFn(Function):
             te, gemb = _grad_target(emb)
             txt_embed_bwd(tokens, dy, V, dy2, _txt_site(noise, pos_off, M * E, p), p, out=te)
         return (None, None, None, None, None, None, None, gemb, None, *grads)
+
+
+# =====================================================================================================
+# The image grid of a set of modality tensors (metrics.Visualization, BaseTrainer.predict)
+# =====================================================================================================
+def image_grid_shape(shapes, nrow, padding=2):
+    """(T, Hg, Wg) of the grid of image batches of shapes [(n, c, h, w), ...]: torchvision's make_grid geometry over tiles of the
+    largest height and width (include/mvk.h, mvk_image_grid); a single tile has no border."""
+    shapes = [s for s in shapes if s[0] > 0]
+    T = sum(s[0] for s in shapes)
+    if T == 0:
+        return 0, 0, 0
+    H, W = max(s[2] for s in shapes), max(s[3] for s in shapes)
+    if T == 1:
+        return 1, H, W
+    xmaps = min(int(nrow), T)
+    ymaps = (T + xmaps - 1) // xmaps
+    return T, ymaps * (H + padding) + padding, xmaps * (W + padding) + padding
+
+
+def _image_grid_torch(tensors, nrow, padding, pad_value, want):
+    """The plain-torch path of image_grid (CPU tensors, other dtypes, strided tensors, more sources than the launch takes): adapt_shape,
+    cat, the grid assembled from the padded cells in a handful of tensor operations, the quantisation of the reference."""
+    from .data.datasets.utils import adapt_shape
+
+    data, _ = adapt_shape({i: t.float() for i, t in enumerate(tensors)})
+    x = torch.cat(list(data.values()))
+    T, _, H, W = x.shape
+    if T == 1:
+        grid = x[0].clone()
+    else:
+        xmaps = min(int(nrow), T)
+        ymaps = (T + xmaps - 1) // xmaps
+        pad = torch.nn.functional.pad
+        cells = pad(x, (0, padding, 0, padding), value=pad_value)  # every tile with the border to its right and below it
+        cells = pad(cells, (0, 0, 0, 0, 0, 0, 0, ymaps * xmaps - T), value=pad_value)  # the empty cells of the last row
+        body = cells.view(ymaps, xmaps, 3, H + padding, W + padding).permute(2, 0, 3, 1, 4)
+        grid = pad(body.reshape(3, ymaps * (H + padding), xmaps * (W + padding)), (padding, 0, padding, 0), value=pad_value)
+    image = None
+    if "uint8" in want:
+        q = torch.nan_to_num(grid.mul(255).add_(0.5), nan=0.0, posinf=255.0, neginf=0.0).clamp_(0, 255)
+        image = q.permute(1, 2, 0).to(torch.uint8).contiguous()
+    return (grid if "float" in want else None), image
+
+
+def image_grid(tensors, nrow, padding=2, pad_value=0.0, want=("float", "uint8"), grid_out=None, image_out=None):
+    """The picture of a list of modality tensors, each [n], [n, a], [n, a, b] or [n, c, h, w] as the models hand them out (NOT
+    adapted): brought to three channels, centred in tiles of the largest height and width, tiled `nrow` to a row with `padding`
+    pixels of `pad_value` around every tile -- adapt_shape, torch.cat and torchvision's make_grid of the reference -- and quantised
+    as its `mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(uint8)`.  Returns (grid [3, Hg, Wg] fp32, image [Hg, Wg, 3] uint8)
+    on the tensors' device; `want` names which of the two ("float", "uint8") are made, the other is None.
+
+    Contiguous fp32 tensors on one GPU are ONE launch of mvk_image_grid that writes every element of both outputs once (grid_out /
+    image_out: caller-owned outputs for that path, contiguous, any element offset).  Everything the launch declines -- CPU tensors,
+    other dtypes (computed in fp32), strided tensors, more than GRID_MAX_SOURCES tensors, 3 Hg Wg >= 2^31 -- takes the plain-torch
+    path."""
+    from .data.datasets.utils import as_image_batch
+
+    want = tuple(want)
+    if not want or any(w not in ("float", "uint8") for w in want):
+        raise ValueError(f'image_grid: want must name "float" and / or "uint8", got {want}')
+    if int(nrow) <= 0 or int(padding) < 0:
+        raise ValueError(f"image_grid: nrow must be positive and padding non-negative, got {nrow}, {padding}")
+    srcs = [as_image_batch(t.detach()) for t in tensors]
+    srcs = [t for t in srcs if t.shape[0] > 0]
+    if not srcs:
+        raise ValueError("image_grid: no image to show (the tensors hold no rows)")
+    if any(t.numel() == 0 for t in srcs):
+        raise ValueError("image_grid: a tensor with an empty channel, height or width")
+    T, Hg, Wg = image_grid_shape([tuple(t.shape) for t in srcs], nrow, padding)
+    dev = srcs[0].device
+    fused = (dev.type == "cuda" and len(srcs) <= _lib.GRID_MAX_SOURCES and 3 * Hg * Wg < 2 ** 31
+             and all(t.device == dev and t.dtype == torch.float32 and t.is_contiguous() for t in srcs))
+    if not fused:
+        if grid_out is not None or image_out is not None:
+            raise ValueError("image_grid: grid_out / image_out belong to the fused launch, which declines these tensors")
+        return _image_grid_torch(srcs, nrow, int(padding), float(pad_value), want)
+    grid = image = None
+    if "float" in want:
+        grid = torch.empty(3, Hg, Wg, dtype=torch.float32, device=dev) if grid_out is None else grid_out
+        if grid.dtype != torch.float32 or tuple(grid.shape) != (3, Hg, Wg) or not grid.is_contiguous() or grid.device != dev:
+            raise ValueError(f"image_grid: grid_out must be a contiguous float32 tensor of shape {(3, Hg, Wg)} on {dev}")
+    if "uint8" in want:
+        image = torch.empty(Hg, Wg, 3, dtype=torch.uint8, device=dev) if image_out is None else image_out
+        if image.dtype != torch.uint8 or tuple(image.shape) != (Hg, Wg, 3) or not image.is_contiguous() or image.device != dev:
+            raise ValueError(f"image_grid: image_out must be a contiguous uint8 tensor of shape {(Hg, Wg, 3)} on {dev}")
+    descs = (_lib.GridSrc * len(srcs))()
+    for d, t in zip(descs, srcs):
+        d.data, (d.n, d.c, d.h, d.w) = t.data_ptr(), t.shape
+    call("mvk_image_grid", descs, len(srcs), int(nrow), int(padding), float(pad_value), ptr(grid), ptr(image), stream_ptr())
+    return grid, image

@@ -7,7 +7,8 @@ Kept from the reference: per-device batch size, sh
 (`epoch, dataset_size, uses_ddp, batch_ratio, beta`), `loss_sum` accumulation, division of the epoch loss by
 the FULL dataset length, metric averaging over batches, best-model bookkeeping, checkpoint directory layout,
 DDP gradient AVERAGING (sum all-reduce, 1/world_size folded into Adam), gradient clipping placed before
-`backward()` (a no-op, reproduced by omitting it), `ArithmeticError` on a NaN loss.
+`backward()` (a no-op, reproduced by omitting it), `ArithmeticError` on a NaN loss, `predict` / `steps_predict` (the
+reconstruction pictures of the best model for `on_prediction_step` and as PNGs; each picture is one kernels.image_grid launch).
 Dropped (no effect on results): `torch.cuda.empty_cache()` per step, per-sample `__getitem__` + collate,
 the per-step `.item()` host sync (one sync per epoch unless `sync_every_step=True`).
 """
@@ -524,6 +525,8 @@ class BaseTrainer:
                 self.best_train_loss = epoch_train_loss
                 self._best_model = deepcopy(self.model)
                 self.metrics_best_model = metrics
+            if cfg.steps_predict is not None and (epoch % cfg.steps_predict == 0 or epoch == 1) and self.is_main_process:
+                self._prediction_step(epoch)  # reconstruction pictures of the best model (base_trainer.py:561-579)
             self.callback_handler.on_epoch_end(training_config=cfg)
             if cfg.steps_saving is not None and epoch % cfg.steps_saving == 0 and self.is_main_process:
                 self.save_checkpoint(model=self._best_model, dir_path=self.training_dir, epoch=epoch)
@@ -540,6 +543,56 @@ class BaseTrainer:
         self.callback_handler.on_train_end(cfg)
         self.history = history
         return history
+
+    # -- reconstruction pictures (training_config.steps_predict) ----------------------------------------------------
+    def _picture(self, all_recons, key, tensors, n_data):
+        """One picture of predict(): the float grid [3, Hg, Wg] on the device under all_recons["images"][key] (what callbacks
+        receive) and the uint8 picture of the SAME launch (kernels.image_grid) kept for the PNG."""
+        grid, image = kernels.image_grid(tensors, nrow=n_data)
+        all_recons["images"][key] = grid
+        self.__dict__.setdefault("_predict_bytes", {})[key] = (grid, image)
+
+    def predict(self, model: BaseModel, epoch: int, n_data=8):
+        """Self and cross reconstructions of the first n_data points of the evaluation (else the training) set during training
+        (base_trainer.py:830-917): {"images": {"recon_from_<modality>": grid, ..., "recon_from_all": grid}}, each a float
+        [3, Hg, Wg] tensor on the device -- the true data in the first row (rows, for "all": one per modality), then N = 8 rows
+        per generated modality.  A BaseMultiVAE gets one picture per conditioning modality and the joint one, any other model
+        (CVAE) the joint one.  Runs eagerly on the current stream; `model` is the best model's copy, not the training one."""
+        from ...models.base.base_ae_model import BaseMultiVAE
+
+        model.eval()
+        predict_dataset = self.eval_dataset if self.eval_dataset is not None else self.train_dataset
+        inputs = next(iter(_BatchIterator(predict_dataset, n_data, False, self.device)))
+        plot = getattr(predict_dataset, "transform_for_plotting", None)
+        show = (lambda t, m: plot(t, modality=m)) if plot is not None else (lambda t, m: t)
+        all_recons = {"images": {}}
+        self.__dict__.pop("_predict_bytes", None)
+        with torch.no_grad():
+            if isinstance(model, BaseMultiVAE):  # every one-to-all cross-modal reconstruction
+                for mod in inputs.data:
+                    recon = model.predict(inputs, mod, "all", N=8, flatten=True, ignore_incomplete=True)
+                    tensors = [show(inputs.data[mod], mod)] + [show(recon[m], m) for m in recon]
+                    self._picture(all_recons, f"recon_from_{mod}", tensors, n_data)
+            recon = model.predict(inputs=inputs, cond_mod="all", gen_mod="all", N=8, flatten=True, ignore_incomplete=True)
+            tensors = [show(inputs.data[m], m) for m in inputs.data] + [show(recon[m], m) for m in recon]
+            self._picture(all_recons, "recon_from_all", tensors, n_data)
+        return all_recons
+
+    def _prediction_step(self, epoch):
+        """predict on the best model, the callbacks' on_prediction_step, then <training_dir>/<key>.png for every image."""
+        from PIL import Image
+
+        metrics_media = self.predict(self._best_model, epoch)
+        self.callback_handler.on_prediction_step(self.training_config, metrics_media=metrics_media, global_step=epoch)
+        images = metrics_media.pop("images", {})
+        made = self.__dict__.pop("_predict_bytes", {})
+        for key, grid in images.items():
+            kept = made.get(key)
+            if kept is not None and kept[0] is grid:
+                image = kept[1]
+            else:  # a picture that did not come from _picture (an overridden predict): quantise it as save_image does
+                image = kernels.image_grid([grid.unsqueeze(0)], nrow=1, want=("uint8",))[1]
+            Image.fromarray(image.cpu().numpy()).save(os.path.join(self.training_dir, f"{key}.png"))
 
     def _schedulers_step(self, metrics=None):
         import torch.optim.lr_scheduler as lr_scheduler
