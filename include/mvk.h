@@ -1210,6 +1210,43 @@ int mvk_polyclf_fwd(const float* x, int64_t n, const float* w1, const float* b1,
                     const float* b3, const float* w4, const float* b4, float* logits, int32_t* pred, const int64_t* labels,
                     int64_t label_rows, int64_t* counts, void* stream);
 
+/* PolyMNIST convolutional networks (multivae/models/nn/mmnist.py:36-206): 3x3 / stride 2 / padding 1 convolutions on the map
+ * chain 28 -> 14 -> 7 -> 4 and their transposes with output_padding 0 or 1 (csrc/polyconv.hip).  The big map U is [n,H,W,Cu]
+ * (u_nchw != 0, Cu == 3 only: the image [n,3,H,W]), the small map V is [n,h,w,Cv] with h = (H + 1) / 2, w = (W + 1) / 2; H and
+ * W are always those of the BIG map, which fixes output_padding.  Wref is the parameter in PyTorch's layout, read in place:
+ * Conv2d(Cu, Cv, 3, 2, 1).weight and ConvTranspose2d(Cv, Cu, 3, 2, 1, output_padding).weight are both [Cv][Cu][3][3], and the
+ * transposed layer is the adjoint of the strided one.  fp32 in and out on the exact f32-input MFMA; every entry is one fixed
+ * sequence of operations on its own image (no floating-point atomics, ordered finishes): results are bit-identical from run to
+ * run, and those of down / up and of the fused trunks do not depend on n or on the image's place in a tile.
+ *   mvk_conv3s2_ok     1 where the entries below take the problem: (Cu, Cv) in {(3,32), (32,64), (64,128)}, 1 <= H, W <= 4096.
+ *                      They return MVK_EINVAL where it returns 0.
+ *   mvk_conv3s2_down   V = act(conv(U) + bias) (* v_act'(v_act_src), laid out like V): Conv2d forward, ConvTranspose2d
+ *                      backward-data.  bias and v_act_src may be NULL.
+ *   mvk_conv3s2_up     U = act(convT(V) + bias) (* u_act'(u_act_src), laid out like U): ConvTranspose2d forward, Conv2d
+ *                      backward-data.  Output positions are walked by parity class (1, 2, 2 and 4 taps).
+ *   mvk_conv3s2_wgrad  dWref[Cv][Cu][3][3] (+)= sum over positions of U(gathered) V (accumulate != 0: +=), and with db != NULL
+ *                      db (+)= the per-channel sums of V (db_side 1, [Cv]: the Conv2d bias) or of U (db_side 2, [Cu]: the
+ *                      ConvTranspose2d bias); db_side 0 with db NULL.  Position slices go to slabs in ws (at least
+ *                      9 Cu Cv + 128 floats) and are added in a fixed order; slicing and order depend on the shape and ws_floats alone.
+ *   mvk_polyenc_fwd    no-grad encoder trunk in one launch: x [n,3,28,28] -> 3 x (conv + bias + ReLU) -> h3 [n,4,4,128] (NHWC).
+ *                      A workgroup owns mvk_polyconv_tile() images; the 14x14x32 and 7x7x64 maps stay in LDS.
+ *   mvk_polydec_fwd    the decoder's mirror: h0 [n,4,4,128] (NHWC) -> convT + ReLU (7x7x64) -> convT + ReLU (14x14x32) -> convT
+ *                      -> [n,3,28,28] (NCHW).  Weights w0 [128,64,3,3], w1 [64,32,3,3], w2 [32,3,3,3].
+ * The fused trunks run the layer routine of down / up: their results equal the three layer launches bit for bit.
+ * NHWC operands read four channels at a time must be 16-byte aligned (MVK_EINVAL otherwise); n == 0 is MVK_OK. */
+int mvk_conv3s2_ok(int H, int W, int Cu, int Cv);
+int mvk_polyconv_tile(void);
+int mvk_conv3s2_down(const float* U, const float* Wref, const float* bias, float* V, int n, int H, int W, int Cu, int Cv, int act,
+                     int u_nchw, const float* v_act_src, int v_act, void* stream);
+int mvk_conv3s2_up(const float* V, const float* Wref, const float* bias, float* U, int n, int H, int W, int Cu, int Cv, int act,
+                   int u_nchw, const float* u_act_src, int u_act, void* stream);
+int mvk_conv3s2_wgrad(const float* U, const float* V, float* dWref, float* db, int db_side, int n, int H, int W, int Cu, int Cv,
+                      int u_nchw, int accumulate, float* ws, int64_t ws_floats, void* stream);
+int mvk_polyenc_fwd(const float* x, int64_t n, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* h3, void* stream);
+int mvk_polydec_fwd(const float* h0, int64_t n, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                    const float* b2, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * CUB text encoder (models/nn/cub.py CubTextEncoder): the stages of a post-norm transformer encoder over short sentences
  * that are not GEMMs (csrc/textenc.hip).  tokens [B,S] int64; activations [B,S,E] fp32; the packed in-projection

@@ -247,6 +247,13 @@ PROTOTYPES = {
     "mvk_fd_finish": [_p, _i, _p, _p, _p, _p],
     "mvk_polyclf_tile": [],  # returns the images per workgroup, not a status
     "mvk_polyclf_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p],
+    "mvk_conv3s2_ok": [_i, _i, _i, _i],  # returns 1 / 0, not a status
+    "mvk_polyconv_tile": [],  # returns the images per workgroup of the fused trunks, not a status
+    "mvk_conv3s2_down": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p],
+    "mvk_conv3s2_up": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p],
+    "mvk_conv3s2_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _p],
+    "mvk_polyenc_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
+    "mvk_polydec_fwd": [_p, _i64, _p, _p, _p, _p, _p, _p, _p, _p],
     "mvk_txt_embed_fwd": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _p],
     "mvk_txt_embed_bwd": [_p, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i, _p],
     "mvk_txt_attn_fwd": [_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p],

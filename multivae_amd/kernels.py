@@ -1434,6 +1434,210 @@ def svhn_fused_tail_ok(C4, C3):
 # =====================================================================================================
 # ResNet stacks (models/nn/mmnist.py:214-366, models/nn/cub.py:144-293), NHWC activations
 # =====================================================================================================
+# =====================================================================================================
+# PolyMNIST convolutional networks (models/nn/mmnist.py:36-206): 3x3 / stride 2 / pad 1 on 28 <-> 14 <-> 7 <-> 4 (csrc/polyconv.hip)
+# =====================================================================================================
+def conv3s2_ok(H, W, Cu, Cv):
+    return bool(_lib.load().mvk_conv3s2_ok(int(H), int(W), int(Cu), int(Cv)))
+
+
+def _conv3s2_check(H, W, Cu, Cv):
+    if not conv3s2_ok(H, W, Cu, Cv):
+        raise _lib.MvkError(f"no 3x3 / stride-2 kernel for a {H}x{W} map with channels ({Cu}, {Cv}): mvk_conv3s2_ok")
+
+
+def conv3s2_down(U, wref, bias, n, H, W, Cu, Cv, act=NONE, u_nchw=False, v_act_src=None, v_act=NONE, out=None):
+    """V [n, h, w, Cv] = act(conv(U) + bias) (* v_act'(v_act_src)); U [n, H, W, Cu], or the image [n, Cu, H, W] (u_nchw).  wref: the
+    [Cv, Cu, 3, 3] parameter itself.  Conv2d forward, ConvTranspose2d backward-data."""
+    _conv3s2_check(H, W, Cu, Cv)
+    V = out if out is not None else _new((n, (H + 1) // 2, (W + 1) // 2, Cv), U)
+    call("mvk_conv3s2_down", ptr(U), ptr(wref), ptr(bias), ptr(V), n, H, W, Cu, Cv, act, int(u_nchw), ptr(v_act_src), v_act,
+         stream_ptr())
+    return V
+
+
+def conv3s2_up(V, wref, bias, n, H, W, Cu, Cv, act=NONE, u_nchw=False, u_act_src=None, u_act=NONE, out=None):
+    """U [n, H, W, Cu] (u_nchw: [n, Cu, H, W]) = act(convT(V) + bias) (* u_act'(u_act_src)); V [n, (H+1)//2, (W+1)//2, Cv].  H, W are
+    the output's: output_padding = H - (2 h - 1).  ConvTranspose2d forward, Conv2d backward-data."""
+    _conv3s2_check(H, W, Cu, Cv)
+    U = out if out is not None else _new((n, Cu, H, W) if u_nchw else (n, H, W, Cu), V)
+    call("mvk_conv3s2_up", ptr(V), ptr(wref), ptr(bias), ptr(U), n, H, W, Cu, Cv, act, int(u_nchw), ptr(u_act_src), u_act,
+         stream_ptr())
+    return U
+
+
+def conv3s2_wgrad(U, V, wparam, bparam, n, H, W, Cu, Cv, u_nchw=False, db_side=1):
+    """wparam.grad += sum U(gathered) V, bparam.grad += the channel sums of V (db_side 1: Conv2d) or of U (db_side 2:
+    ConvTranspose2d), straight into the flat gradient buffer where the trainer provides one -> (grad for w, grad for b)."""
+    _conv3s2_check(H, W, Cu, Cv)
+    dw, rw = _grad_target(wparam)
+    db, rb = _grad_target(bparam) if bparam is not None else (None, None)
+    ws = _ws(V)
+    call("mvk_conv3s2_wgrad", ptr(U), ptr(V), ptr(dw), ptr(db), db_side if bparam is not None else 0, n, H, W, Cu, Cv,
+         int(u_nchw), 1, ptr(ws), ws.numel(), stream_ptr())
+    return rw, rb
+
+
+POLYCONV_CHANS = (3, 32, 64, 128)
+POLYCONV_MAPS = (28, 14, 7, 4)
+
+
+def _polyconv_check(x_shape, ws, transposed):
+    c = POLYCONV_CHANS
+    want = [((c[i + 1], c[i], 3, 3), (c[i + 1],)) for i in range(3)]
+    if transposed:
+        want = [((c[3 - i], c[2 - i], 3, 3), (c[2 - i],)) for i in range(3)]
+    got = [(tuple(ws[2 * i].shape), tuple(ws[2 * i + 1].shape)) for i in range(3)]
+    if got != want:
+        raise _lib.MvkError(f"PolyMNIST convolutional trunk: parameter shapes {got}, expected {want}")
+    if tuple(x_shape[1:]) != ((4, 4, 128) if transposed else (3, 28, 28)):
+        raise _lib.MvkError(f"PolyMNIST convolutional trunk: input {tuple(x_shape)}")
+
+
+def polyenc_forward(x, w0, b0, w1, b1, w2, b2):
+    """The no-grad encoder trunk in one launch (mvk_polyenc_fwd): x [n, 3, 28, 28] -> h3 [n, 4, 4, 128] (NHWC, after its ReLU)."""
+    x = _c(x)
+    _polyconv_check(x.shape, (w0, b0, w1, b1, w2, b2), False)
+    h3 = _new((x.shape[0], 4, 4, 128), x)
+    call("mvk_polyenc_fwd", ptr(x), x.shape[0], ptr(_c(w0)), ptr(_c(b0)), ptr(_c(w1)), ptr(_c(b1)), ptr(_c(w2)), ptr(_c(b2)),
+         ptr(h3), stream_ptr())
+    return h3
+
+
+def polydec_forward(h0, w0, b0, w1, b1, w2, b2):
+    """The no-grad decoder trunk in one launch (mvk_polydec_fwd): h0 [n, 4, 4, 128] (NHWC) -> [n, 3, 28, 28]."""
+    h0 = _c(h0)
+    _polyconv_check(h0.shape, (w0, b0, w1, b1, w2, b2), True)
+    out = _new((h0.shape[0], 3, 28, 28), h0)
+    call("mvk_polydec_fwd", ptr(h0), h0.shape[0], ptr(_c(w0)), ptr(_c(b0)), ptr(_c(w1)), ptr(_c(b1)), ptr(_c(w2)), ptr(_c(b2)),
+         ptr(out), stream_ptr())
+    return out
+
+
+class PolyConvEncoderFn(Function):
+    """x [n, 3, 28, 28] NCHW -> 3 x (Conv 3/2/1 + ReLU) -> h3 [n, 4, 4, 128] NHWC (the heads are the caller's).  Without a
+    gradient to keep anything for, the whole trunk is one launch."""
+
+    @classmethod
+    def run(cls, x, *params):
+        """`apply`, or the fused trunk under torch.no_grad() (grad mode is always off INSIDE forward: only the caller can look)."""
+        return cls.apply(x, *params) if torch.is_grad_enabled() else polyenc_forward(x, *params)
+
+    @staticmethod
+    def forward(ctx, x, w0, b0, w1, b1, w2, b2):
+        x = _c(x)
+        params = (w0, b0, w1, b1, w2, b2)
+        _polyconv_check(x.shape, params, False)
+        if not any(ctx.needs_input_grad):  # nothing is kept for a backward pass
+            return polyenc_forward(x, *params)
+        n = x.shape[0]
+        c, m = POLYCONV_CHANS, POLYCONV_MAPS
+        h1 = conv3s2_down(x, w0, b0, n, m[0], m[0], c[0], c[1], RELU, u_nchw=True)
+        h2 = conv3s2_down(h1, w1, b1, n, m[1], m[1], c[1], c[2], RELU)
+        h3 = conv3s2_down(h2, w2, b2, n, m[2], m[2], c[2], c[3], RELU)
+        ctx.save_for_backward(x, h1, h2, h3, *params)
+        _tap("polyconv_encoder", w0, h1, h2, h3)  # NHWC
+        return h3
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dh3):
+        x, h1, h2, h3, w0, b0, w1, b1, w2, b2 = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise _lib.MvkError("gradient w.r.t. the encoder input image is not implemented")
+        n = x.shape[0]
+        c, m = POLYCONV_CHANS, POLYCONV_MAPS
+        schedule.defer_flush_sibling(x.device, node_params=(w0, b0, w1, b1, w2, b2))
+        dp3 = torch.empty_like(h3)
+        call("mvk_act_bwd_scaled", ptr(_c(dh3)), 1.0, ptr(h3), RELU, ptr(dp3), h3.numel(), stream_ptr())
+        # each backward-data launch is followed by the weight gradient of the layer below it
+        dw2, db2 = conv3s2_wgrad(h2, dp3, w2, b2, n, m[2], m[2], c[2], c[3])
+        dp2 = conv3s2_up(dp3, w2, None, n, m[2], m[2], c[2], c[3], u_act_src=h2, u_act=RELU)
+        dw1, db1 = conv3s2_wgrad(h1, dp2, w1, b1, n, m[1], m[1], c[1], c[2])
+        dp1 = conv3s2_up(dp2, w1, None, n, m[1], m[1], c[1], c[2], u_act_src=h1, u_act=RELU)
+        dw0, db0 = conv3s2_wgrad(x, dp1, w0, b0, n, m[0], m[0], c[0], c[1], u_nchw=True)
+        return None, dw0, db0, dw1, db1, dw2, db2
+
+
+class PolyConvDecoderFn(Function):
+    """h0 [n, 4, 4, 128] NHWC (after the ReLU of the linear layer) -> ConvT(128, 64) + ReLU -> ConvT(64, 32, op 1) + ReLU ->
+    ConvT(32, 3, op 1) -> [n, 3, 28, 28] NCHW.  Its backward reads the images' gradient only (there is no fused likelihood
+    tail, so no row gradient of the loss assembly is read and nothing has to wait for it)."""
+
+    @classmethod
+    def run(cls, h0, *params):
+        """`apply`, or the fused trunk under torch.no_grad()."""
+        return cls.apply(h0, *params) if torch.is_grad_enabled() else polydec_forward(h0, *params)
+
+    @staticmethod
+    def forward(ctx, h0, w0, b0, w1, b1, w2, b2):
+        h0 = _c(h0)
+        params = (w0, b0, w1, b1, w2, b2)
+        _polyconv_check(h0.shape, params, True)
+        if not any(ctx.needs_input_grad):  # nothing is kept for a backward pass
+            return polydec_forward(h0, *params)
+        n = h0.shape[0]
+        c, m = POLYCONV_CHANS, POLYCONV_MAPS
+        d1 = conv3s2_up(h0, w0, b0, n, m[2], m[2], c[2], c[3], RELU)
+        d2 = conv3s2_up(d1, w1, b1, n, m[1], m[1], c[1], c[2], RELU)
+        out = conv3s2_up(d2, w2, b2, n, m[0], m[0], c[0], c[1], NONE, u_nchw=True)
+        ctx.save_for_backward(h0, d1, d2, *params)
+        _tap("polyconv_decoder", w0, d1, d2)  # NHWC
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        h0, d1, d2, w0, b0, w1, b1, w2, b2 = ctx.saved_tensors
+        n = h0.shape[0]
+        c, m = POLYCONV_CHANS, POLYCONV_MAPS
+        dout = _c(dout)
+        # the image layer has no activation: dout is its pre-activation gradient
+        dw2, db2 = conv3s2_wgrad(dout, d2, w2, b2, n, m[0], m[0], c[0], c[1], u_nchw=True, db_side=2)
+        dp2 = conv3s2_down(dout, w2, None, n, m[0], m[0], c[0], c[1], u_nchw=True, v_act_src=d2, v_act=RELU)
+        dw1, db1 = conv3s2_wgrad(dp2, d1, w1, b1, n, m[1], m[1], c[1], c[2], db_side=2)
+        dp1 = conv3s2_down(dp2, w1, None, n, m[1], m[1], c[1], c[2], v_act_src=d1, v_act=RELU)
+        dw0, db0 = conv3s2_wgrad(dp1, h0, w0, b0, n, m[2], m[2], c[2], c[3], db_side=2)
+        dh0 = conv3s2_down(dp1, w0, None, n, m[2], m[2], c[2], c[3]) if ctx.needs_input_grad[0] else None
+        return dh0, dw0, db0, dw1, db1, dw2, db2
+
+
+class PolyConvHeadsFn(Function):
+    """The two Conv2d(128, L, 4, 2, 0) heads on the 4x4 map (mmnist.py:101-102): a window that covers the whole map is a linear layer
+    over the map flattened in (c, h, w) order, which is the parameter's own layout [L, 128 * 16].  flat [n, 2048] -> (mu, lv) [n, L];
+    the weight gradients land in the 4-d parameters' own gradient buffers."""
+
+    @staticmethod
+    def forward(ctx, flat, w_mu, b_mu, w_lv, b_lv):
+        flat = _c(flat)
+        L, Kf = w_mu.shape[0], flat.shape[1]
+        if w_mu[0].numel() != Kf or w_lv.shape != w_mu.shape:
+            raise _lib.MvkError(f"heads {tuple(w_mu.shape)} / {tuple(w_lv.shape)} on a flattened map of {Kf}")
+        mu = linear_fwd(flat, w_mu.detach().view(L, Kf), b_mu, NONE)
+        lv = linear_fwd(flat, w_lv.detach().view(L, Kf), b_lv, NONE)
+        ctx.save_for_backward(flat, w_mu, b_mu, w_lv, b_lv)
+        return mu, lv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dmu, dlv):
+        flat, w_mu, b_mu, w_lv, b_lv = ctx.saved_tensors
+        L, Kf = w_mu.shape[0], flat.shape[1]
+        dys, w2 = [_c(dmu), _c(dlv)], [w_mu.detach().view(L, Kf), w_lv.detach().view(L, Kf)]
+        need_dx = ctx.needs_input_grad[0]
+        fused = heads_bwd(flat, NONE, dys, w2, [b_mu, b_lv], 1, Kf, want_dx=need_dx, dw_params=[w_mu, w_lv]) if need_dx else None
+        if fused is not None:
+            dflat, (dw_mu, dw_lv), (db_mu, db_lv), _ = fused
+            return dflat, dw_mu, db_mu, dw_lv, db_lv
+        dw_mu, db_mu = linear_bwd_weight(dys[0], flat, w_mu, b_mu)
+        dw_lv, db_lv = linear_bwd_weight(dys[1], flat, w_lv, b_lv)
+        dflat = None
+        if need_dx:
+            dflat = linear_bwd_data(dys[0], w2[0])
+            linear_bwd_data(dys[1], w2[1], out=dflat, accumulate=True)
+        return dflat, dw_mu, db_mu, dw_lv, db_lv
+
+
 def _rs_conv(pool, X, xam, wpack, bias, n, H, W, Cin, Cout, **kw):
     """One 3x3 convolution of a ResNet stack -> (result of conv3x3 / conv3x3_f, amax slot of Y or None).  With a pool (the
     scaled-fp16 form is on) and a covered shape the launch is mvk_conv3x3_s: xam = the slot that bounds max |X| (None: it is

@@ -1,7 +1,14 @@
-"""PolyMNIST ResNet architectures of MMVAE+ (`multivae/models/nn/mmnist.py:214-366`, adapted there from
-github.com/epalu/mmvaeplus) on the HIP kernels: 3x3 convolutions on the implicit-GEMM engine, AvgPool / Upsample /
-residual kernels, the whole convolutional stack of a network as ONE autograd node (kernels.ResnetStackFn).  Module
-structure and parameter names follow the reference, so its state_dicts load unchanged."""
+"""PolyMNIST architectures (`multivae/models/nn/mmnist.py`) on the HIP kernels.
+
+The convolutional networks (`:36-206`): three 3x3 / stride-2 layers on 28 -> 14 -> 7 -> 4 and their transposes, one autograd
+node per trunk (kernels.PolyConvEncoderFn / PolyConvDecoderFn on csrc/polyconv.hip; without a gradient the trunk is one
+launch), the linear layers and heads on kernels.MLPHeadsFn.
+
+The ResNet architectures of MMVAE+ (`:214-366`, adapted there from github.com/epalu/mmvaeplus): 3x3 convolutions on the
+implicit-GEMM engine, AvgPool / Upsample / residual kernels, the whole convolutional stack of a network as ONE autograd node
+(kernels.ResnetStackFn).
+
+Module structure and parameter names follow the reference, so its state_dicts load unchanged."""
 import numpy as np
 import torch
 from torch import nn
@@ -9,6 +16,139 @@ from torch import nn
 from ... import kernels
 from ..base.base_utils import ModelOutput
 from .base_architectures import BaseDecoder, BaseEncoder
+
+
+class Flatten(torch.nn.Module):
+    """`mmnist.py:13-17`."""
+
+    def forward(self, x):
+        return x.view(x.size(0), -1)
+
+
+class Unflatten(torch.nn.Module):
+    """`mmnist.py:20-28`."""
+
+    def __init__(self, ndims):
+        super(Unflatten, self).__init__()
+        self.ndims = ndims
+
+    def forward(self, x):
+        return x.view(x.size(0), *self.ndims)
+
+
+def _conv_trunk():
+    """The three Conv2d(3, 2, 1) + ReLU layers every convolutional encoder starts with (parameter containers)."""
+    return [nn.Conv2d(3, 32, kernel_size=3, stride=2, padding=1, bias=True), nn.ReLU(),
+            nn.Conv2d(32, 64, kernel_size=3, stride=2, padding=1, bias=True), nn.ReLU(),
+            nn.Conv2d(64, 128, kernel_size=3, stride=2, padding=1, bias=True), nn.ReLU()]
+
+
+def _trunk_flat(x, seq):
+    """x [n, 3, 28, 28] -> the trunk's output flattened in the reference's NCHW order [n, 2048]."""
+    h3 = kernels.PolyConvEncoderFn.run(x, seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias, seq[4].weight, seq[4].bias)
+    return kernels.nhwc_to_flat_nchw(h3)
+
+
+def _conv_heads(flat, c_mu, c_lv):
+    """The two Conv2d(128, L, 4, 2, 0) heads on the 4x4 map: one linear layer each over the flattened map -> [n, L, 1, 1]."""
+    L = c_mu.weight.shape[0]
+    mu, lv = kernels.PolyConvHeadsFn.apply(flat, c_mu.weight, c_mu.bias, c_lv.weight, c_lv.bias)
+    return mu.reshape(-1, L, 1, 1), lv.reshape(-1, L, 1, 1)
+
+
+class EncoderConvMMNIST(BaseEncoder):
+    """`mmnist.py:36-75`: trunk -> nn.Flatten -> Linear(2048, L) + ReLU -> bias-free class_mu / class_logvar."""
+
+    def __init__(self, model_config, bias=False):
+        super(EncoderConvMMNIST, self).__init__()
+        self.latent_dim = model_config.latent_dim
+        self.shared_encoder = nn.Sequential(*_conv_trunk(), nn.Flatten(), nn.Linear(2048, self.latent_dim), nn.ReLU())
+        self.class_mu = nn.Linear(self.latent_dim, self.latent_dim, bias=bias)
+        self.class_logvar = nn.Linear(self.latent_dim, self.latent_dim, bias=bias)
+
+    def forward(self, x):
+        e = self.shared_encoder
+        mu, lv = kernels.MLPHeadsFn.apply(_trunk_flat(x, e), 2, e[7].weight, e[7].bias, self.class_mu.weight, self.class_mu.bias,
+                                          self.class_logvar.weight, self.class_logvar.bias)
+        return ModelOutput(embedding=mu, log_covariance=lv)
+
+
+class EncoderConvMMNIST_adapted(BaseEncoder):
+    """`mmnist.py:78-109`: trunk -> two Conv2d(128, L, 4, 2, 0) heads; the reference squeezes ALL unit dims of [n, L, 1, 1]."""
+
+    def __init__(self, model_config):
+        super(EncoderConvMMNIST_adapted, self).__init__()
+        self.latent_dim = model_config.latent_dim
+        self.style_dim = 0
+        self.shared_encoder = nn.Sequential(*_conv_trunk())
+        self.class_mu = nn.Conv2d(128, self.latent_dim, 4, 2, 0)
+        self.class_logvar = nn.Conv2d(128, self.latent_dim, 4, 2, 0)
+
+    def forward(self, x):
+        mu, lv = _conv_heads(_trunk_flat(x, self.shared_encoder), self.class_mu, self.class_logvar)
+        return ModelOutput(embedding=mu.squeeze(), log_covariance=lv.squeeze())
+
+
+class EncoderConvMMNIST_multilatents(BaseEncoder):
+    """`mmnist.py:112-170`: a content trunk with heads and, with style_dim > 0, a style trunk with heads."""
+
+    def __init__(self, model_config):
+        super(EncoderConvMMNIST_multilatents, self).__init__()
+        self.latent_dim = model_config.latent_dim
+        self.style_dim = model_config.style_dim
+        self.encoder_class = nn.Sequential(*_conv_trunk())
+        self.class_mu = nn.Conv2d(128, self.latent_dim, 4, 2, 0)
+        self.class_logvar = nn.Conv2d(128, self.latent_dim, 4, 2, 0)
+        if self.style_dim > 0:
+            self.encoder_style = nn.Sequential(*_conv_trunk())
+            self.style_mu = nn.Conv2d(128, self.style_dim, 4, 2, 0)
+            self.style_logvar = nn.Conv2d(128, self.style_dim, 4, 2, 0)
+
+    def forward(self, x):
+        output = ModelOutput()
+        mu, lv = _conv_heads(_trunk_flat(x, self.encoder_class), self.class_mu, self.class_logvar)
+        output["embedding"] = mu.squeeze(-1, -2)
+        output["log_covariance"] = lv.squeeze(-1, -2)
+        if self.style_dim > 0:
+            smu, slv = _conv_heads(_trunk_flat(x, self.encoder_style), self.style_mu, self.style_logvar)
+            output["style_embedding"] = smu.squeeze(-1, -2)
+            output["style_log_covariance"] = slv.squeeze(-1, -2)
+        return output
+
+
+class DecoderConvMMNIST(BaseDecoder):
+    """`mmnist.py:173-206`: Linear(L, 2048) + ReLU -> Unflatten (128, 4, 4) -> ConvT(128, 64) + ReLU -> ConvT(64, 32, op 1) + ReLU ->
+    ConvT(32, 3, op 1), no output activation."""
+    rows_independent = True
+
+    def __init__(self, model_config):
+        super(DecoderConvMMNIST, self).__init__()
+        self.latent_dim = model_config.latent_dim
+        self.decoder = nn.Sequential(
+            nn.Linear(self.latent_dim, 2048), nn.ReLU(), Unflatten((128, 4, 4)),
+            nn.ConvTranspose2d(128, 64, kernel_size=3, stride=2, padding=1), nn.ReLU(),
+            nn.ConvTranspose2d(64, 32, kernel_size=3, stride=2, padding=1, output_padding=1), nn.ReLU(),
+            nn.ConvTranspose2d(32, 3, kernel_size=3, stride=2, padding=1, output_padding=1),
+        )
+
+    def late_leaf_params(self):
+        """The transposed convolutions' weights: their gradients are leaves of the backward pass (trainers.FlatParams keeps them
+        together at the end of its buffers, as for Decoder_VAE_SVHN)."""
+        d = self.decoder
+        return [d[3].weight, d[5].weight, d[7].weight]
+
+    def forward(self, z):
+        d = self.decoder
+        z2 = z.reshape(-1, z.shape[-1])
+        (pre,) = kernels.MLPHeadsFn.apply(z2, 1, d[0].weight, d[0].bias)  # [N, 2048] in (c, h, w) order, before the ReLU
+        h0 = kernels.TransposeActFn.apply(pre.reshape(-1, 128, 16), kernels.RELU).reshape(-1, 4, 4, 128)  # ReLU on the way to NHWC
+        out = kernels.PolyConvDecoderFn.run(h0, d[3].weight, d[3].bias, d[5].weight, d[5].bias, d[7].weight, d[7].bias)
+        return ModelOutput(reconstruction=out.reshape(*z.shape[:-1], *out.shape[1:]))
+
+
+###############################################################################
+### ResNet architectures
+###############################################################################
 
 
 class ResnetBlock(nn.Module):
