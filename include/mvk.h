@@ -1336,6 +1336,28 @@ int mvk_image_grid_size(const mvk_grid_src* srcs, int S, int nrow, int padding, 
 int mvk_image_grid(const mvk_grid_src* srcs, int S, int nrow, int padding, float pad_value, float* grid, uint8_t* image,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * A batch of a device-resident dataset (data/datasets/cub.py, CUB.device_batcher)
+ * ------------------------------------------------------------------------------------------------ */
+/* The rows of a store picked by a device index tensor, expanded to what the models take; one launch each, on the caller's
+ * stream, nothing synchronises.  Every output element is written exactly once (no memset in front, no atomics); the outputs
+ * may begin at any 4-byte (out_tokens: 8-byte) aligned address.  The indices are taken ON TRUST: the caller checks
+ * 0 <= index[b] < N (captions) and index[b] / div < N (images) on the host before it copies an epoch's order to the device.
+ *
+ * mvk_text_batch: the captions of a batch, with r = index[b]:
+ *   out_tokens[b, l]   = tokens[r, l]                       int64 [B, L], or NULL
+ *   padding_mask[b, l] = l < lengths[r] ? 1 : 0             fp32 [B, L]
+ *   one_hot[b, l, c]   = c == tokens[r, l] ? 1 : 0          fp32 [B, L, V], or NULL (a token outside [0, V) gives a zero row)
+ * mvk_u8_image_batch: the pictures of a batch from a byte store [N, E]:
+ *   out[b, e] = float(store[index[b] / div, e]) / 255       fp32 [B, E]; the IEEE division, bit for bit torch's
+ *                                                           .float().div(255); div = 10: the ten captions of a CUB picture
+ * B == 0 returns MVK_OK without a launch.  MVK_EINVAL: a NULL required pointer, L < 1, V < 1, E < 1, div < 1, a negative
+ * B or N, N == 0 with B > 0, a misaligned output. */
+int mvk_text_batch(const int32_t* tokens, const int32_t* lengths, const int64_t* index, int64_t N, int B, int L, int V,
+                   int64_t* out_tokens, float* padding_mask, float* one_hot, void* stream);
+int mvk_u8_image_batch(const uint8_t* store, const int64_t* index, int64_t N, int B, int64_t E, int div, float* out,
+                       void* stream);
+
 /* Device-timestamp profiler (bench.py's roofline objects).  device_slots: nslots records of MVK_PROF_SLOT_U64 = 520
  * uint64 each: [0] sum of durations (clock ticks, first workgroup in -> last workgroup out), [1] launches accumulated,
  * [2] sum of (first workgroup in -> start of the one-wave fold kernel queued behind the launch: the launch has drained

@@ -263,6 +263,8 @@ PROTOTYPES = {
     "mvk_txt_drop": [_p, _p, _f, _i64, _p],
     "mvk_image_grid_size": [C.POINTER(GridSrc), _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "mvk_image_grid": [C.POINTER(GridSrc), _i, _i, _i, _f, _p, _p, _p],
+    "mvk_text_batch": [_p, _p, _p, _i64, _i, _i, _i, _p, _p, _p, _p],
+    "mvk_u8_image_batch": [_p, _p, _i64, _i, _i64, _i, _p, _p],
 }
 GRID_MAX_SOURCES = 32  # MVK_GRID_MAX_SOURCES
 TXT_MAX_SEQ, TXT_MAX_HEAD_DIM = 64, 128  # MVK_TXT_MAX_SEQ / MVK_TXT_MAX_HEAD_DIM

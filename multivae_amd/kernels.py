@@ -3661,3 +3661,42 @@ def image_grid(tensors, nrow, padding=2, pad_value=0.0, want=("float", "uint8"),
         d.data, (d.n, d.c, d.h, d.w) = t.data_ptr(), t.shape
     call("mvk_image_grid", descs, len(srcs), int(nrow), int(padding), float(pad_value), ptr(grid), ptr(image), stream_ptr())
     return grid, image
+
+
+# =====================================================================================================
+# A batch of a device-resident dataset (data/datasets/cub.py, CUB.device_batcher)
+# =====================================================================================================
+def text_batch(tokens, lengths, index, vocab_size, want=("tokens", "padding_mask", "one_hot")):
+    """The captions `index` (int64 [B], on the device, in [0, N): taken on trust) of a token store (`tokens` int32 [N, L],
+    `lengths` int32 [N]) in ONE launch of mvk_text_batch: dict(tokens=int64 [B, L], padding_mask=fp32 [B, L], one_hot=fp32
+    [B, L, V]) with the entries `want` names ("padding_mask" is always made)."""
+    if tokens.dtype != torch.int32 or lengths.dtype != torch.int32 or index.dtype != torch.int64:
+        raise ValueError("text_batch: tokens and lengths are int32, the index int64")
+    if not (tokens.is_cuda and tokens.is_contiguous() and lengths.is_contiguous() and index.is_contiguous()
+            and lengths.device == tokens.device and index.device == tokens.device):
+        raise _lib.MvkError("text_batch: contiguous tensors on one GPU")
+    N, L = tokens.shape
+    B, V = index.numel(), int(vocab_size)
+    out = {}
+    if "tokens" in want:
+        out["tokens"] = torch.empty(B, L, dtype=torch.int64, device=tokens.device)
+    out["padding_mask"] = torch.empty(B, L, dtype=torch.float32, device=tokens.device)
+    if "one_hot" in want:
+        out["one_hot"] = torch.empty(B, L, V, dtype=torch.float32, device=tokens.device)
+    call("mvk_text_batch", ptr(tokens), ptr(lengths), ptr(index), N, B, L, V, ptr(out.get("tokens")), ptr(out["padding_mask"]),
+         ptr(out.get("one_hot")), stream_ptr())
+    return out
+
+
+def u8_image_batch(store, index, div=1):
+    """Rows `index // div` (int64 [B], on the device: taken on trust) of a byte store [N, ...] as fp32 in [0, 1]: ONE launch of
+    mvk_u8_image_batch, bit for bit `store[index // div].float().div(255)`."""
+    if store.dtype != torch.uint8 or index.dtype != torch.int64:
+        raise ValueError("u8_image_batch: a uint8 store and an int64 index")
+    if not (store.is_cuda and store.is_contiguous() and index.is_contiguous() and index.device == store.device):
+        raise _lib.MvkError("u8_image_batch: contiguous tensors on one GPU")
+    N, B = store.shape[0], index.numel()
+    E = store[0].numel() if N else 0
+    out = torch.empty((B, *store.shape[1:]), dtype=torch.float32, device=store.device)
+    call("mvk_u8_image_batch", ptr(store), ptr(index), N, B, E, int(div), ptr(out), stream_ptr())
+    return out
