@@ -6,24 +6,12 @@
 // are scored by the modality's own posterior (lqw), the prior terms are weighted by beta, and the private part of a
 // cross-modal decoder input is sampled from the target modality's prior (cross_latent kernels).  All tensors are small ([K,B,L], L ~ 20-64): these kernels are
 // latency-bound; the design goal is few launches and deterministic reductions.
+// The mixture-of-experts stage of latent_fwd_kernel / latent_bwd_kernel, their pointer tables and the entry points' common
+// argument checks live in latent.hpp, shared with cmvae.hip; the two kernels here supply the learnable prior.
 #include "common.hpp"
-#include "latent.hpp"  // lat_logp, lat_dlogp_dz, lat_dlogp_dsd, lat_t
+#include "latent.hpp"
 
 namespace {
-
-constexpr int MAXM = MVK_MAX_MODALITIES;
-
-struct MmPtrs {
-  const float* mu[MAXM];
-  const float* sd[MAXM];
-  const float* noise[MAXM];
-  const uint8_t* mask[MAXM];
-  float* z[MAXM];
-  float* lpz[MAXM];
-  float* lqz[MAXM];
-  float* lq_all[MAXM];
-  float* lqw[MAXM];  // MMVAE+: log q_c(w_c) rows (NULL for MMVAE)
-};
 
 // ---- std from log-variance ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void std_fwd_kernel(const float* __restrict__ lv, int rows, int L, int family,
@@ -89,8 +77,9 @@ __global__ __launch_bounds__(256) void std_bwd_kernel(const float* __restrict__ 
 }
 
 // ---- forward: samples, prior log-density, mixture log-density --------------------------------------------------
-// one wave per (c, k, b); lanes over l
-__global__ __launch_bounds__(256) void latent_fwd_kernel(const MmPtrs p, const float* __restrict__ prior_mean,
+// one wave per (c, k, b); lanes over l.  The mixture-of-experts stage is latent.hpp's; the prior here is one learnable
+// family(prior_mean, prior_sd) over all L dims.
+__global__ __launch_bounds__(256) void latent_fwd_kernel(const LatFwdPtrs p, const float* __restrict__ prior_mean,
                                                          const float* __restrict__ prior_sd, int M, int K, int B,
                                                          int L, int Ls, int family) {
   const int lane = threadIdx.x & 63;
@@ -100,73 +89,16 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(const MmPtrs p, const f
   const int c = (int)(row / ((long long)K * B));
   const int kb = (int)(row % ((long long)K * B));
   const int b = kb % B;
-  float lp = 0.f, lqw = 0.f;
+  float lp = 0.f, lqw;
   float lq[MAXM];
-#pragma unroll
-  for (int m = 0; m < MAXM; ++m) lq[m] = 0.f;
-  // static selection of the conditioning modality's pointers
-  const float* mu_c = nullptr;
-  const float* sd_c = nullptr;
-  const float* nz_c = nullptr;
-  float* z_c = nullptr;
-#pragma unroll
-  for (int m = 0; m < MAXM; ++m)
-    if (m == c) {
-      mu_c = p.mu[m];
-      sd_c = p.sd[m];
-      nz_c = p.noise[m];
-      z_c = p.z[m];
-    }
-  for (int l = lane; l < L; l += 64) {
-    const long long o = (long long)b * L + l;
-    const long long zo = (long long)kb * L + l;
-    const float z = mu_c[o] + sd_c[o] * lat_t(family, nz_c[zo]);
-    z_c[zo] = z;
-    lp += lat_logp(family, z, prior_mean[l], prior_sd[l]);
-    if (l < Ls) {  // shared dims: every modality's posterior enters the mixture
-#pragma unroll
-      for (int m = 0; m < MAXM; ++m)
-        if (m < M) lq[m] += lat_logp(family, z, p.mu[m][o], p.sd[m][o]);
-    } else {  // private dims (MMVAE+): the conditioning modality's own posterior
-      lqw += lat_logp(family, z, mu_c[o], sd_c[o]);
-    }
-  }
+  lat_fwd_dims(p, M, L, Ls, family, c, kb, b, lane, lq, lqw,
+               [&](int l, float z) { lp += lat_logp(family, z, prior_mean[l], prior_sd[l]); });
   lp = wave_sum(lp);
   lqw = wave_sum(lqw);
-  int navail = 0;
-  float mx = -INFINITY;
-#pragma unroll
-  for (int m = 0; m < MAXM; ++m) {
-    if (m < M) {
-      lq[m] = wave_sum(lq[m]);
-      const bool av = p.mask[m] ? p.mask[m][b] != 0 : true;
-      if (!av) lq[m] = -INFINITY;  // mmvae_model.py:195
-      navail += av ? 1 : 0;
-      mx = fmaxf(mx, lq[m]);
-    }
-  }
-  if (lane == 0) {
-    float s = 0.f;
-#pragma unroll
-    for (int m = 0; m < MAXM; ++m)
-      if (m < M) s += expf(lq[m] - mx);
-    const float lse = mx + logf(s);
-#pragma unroll
-    for (int m = 0; m < MAXM; ++m) {
-      if (m == c) {
-        p.lpz[m][kb] = lp;
-        p.lqz[m][kb] = lse - logf((float)navail);
-        if (p.lqw[m]) p.lqw[m][kb] = lqw;
-        for (int mm = 0; mm < M; ++mm) {
-          float v = 0.f;
-#pragma unroll
-          for (int q = 0; q < MAXM; ++q)
-            if (q == mm) v = lq[q];
-          p.lq_all[m][(long long)mm * K * B + kb] = v;
-        }
-      }
-    }
-  }
+  lat_fwd_finish(p, M, K, B, c, kb, b, lane, lq, [&](int m) {
+    p.lpz[m][kb] = lp;
+    if (p.lqw[m]) p.lqw[m][kb] = lqw;  // NULL for MMVAE
+  });
 }
 
 // ---- objective: lw, softmax weights over K, loss -------------------------------------------------------------
@@ -240,22 +172,8 @@ __global__ __launch_bounds__(1024) void objective_kernel(const ObjPtrs p, int M,
 }
 
 // ---- backward on the latent side ------------------------------------------------------------------------------
-struct BwdPtrs {
-  const float* mu[MAXM];
-  const float* sd[MAXM];
-  const float* noise[MAXM];
-  const float* z[MAXM];
-  const uint8_t* mask[MAXM];
-  const float* w[MAXM];
-  const float* lq_all[MAXM];
-  const float* lqz[MAXM];
-  const float* dz_dec[MAXM];
-  float* dmu[MAXM];
-  float* dsd[MAXM];
-};
-
-// one wave per batch row b; lanes over l; loops over conditioning modality c and sample k
-__global__ __launch_bounds__(256) void latent_bwd_kernel(const BwdPtrs p, const float* __restrict__ prior_mean,
+// one wave per batch row b; lanes over l; lat_bwd_dim (latent.hpp) loops over conditioning modality c and sample k
+__global__ __launch_bounds__(256) void latent_bwd_kernel(const LatBwdPtrs p, const float* __restrict__ prior_mean,
                                                          const float* __restrict__ prior_sd, int M, int K, int B,
                                                          int L, int Ls, float beta, int family, int dreg,
                                                          const float* __restrict__ gscale,
@@ -264,76 +182,18 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(const BwdPtrs p, const 
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   const float gs = gscale ? *gscale : 1.0f;
-  int navail = 0;
   bool avail[MAXM];
-#pragma unroll
-  for (int m = 0; m < MAXM; ++m) {
-    avail[m] = (m < M) && (p.mask[m] ? p.mask[m][b] != 0 : true);
-    navail += avail[m] ? 1 : 0;
-  }
+  const int navail = lat_avail(p.mask, M, b, avail);
   const float inv_n = 1.0f / (float)navail;
   for (int l = lane; l < L; l += 64) {
-    const long long o = (long long)b * L + l;
-    float mu[MAXM], sd[MAXM], dmu[MAXM], dsd[MAXM];
-#pragma unroll
-    for (int m = 0; m < MAXM; ++m) {
-      mu[m] = (m < M) ? p.mu[m][o] : 0.f;
-      sd[m] = (m < M) ? p.sd[m][o] : 1.f;
-      dmu[m] = 0.f;
-      dsd[m] = 0.f;
-    }
     const float pm = prior_mean[l], ps = prior_sd[l];
     float dps = 0.f;
-#pragma unroll
-    for (int c = 0; c < MAXM; ++c) {
-      if (c < M && avail[c]) {  // rows with mask_c == 0 have lw == 0 identically: no gradient
-        for (int k = 0; k < K; ++k) {
-          const long long kb = (long long)k * B + b;
-          const long long zo = kb * L + l;
-          const float wk = p.w[c][kb];
-          const float g = -gs * inv_n * wk * beta;  // dLoss / d lw[c][k,b] times the weight of the latent terms
-          const float z = p.z[c][zo];
-          // prior
-          float gz = g * lat_dlogp_dz(family, z, pm, ps);
-          dps += g * lat_dlogp_dsd(family, z, pm, ps);
-          // mixture posterior: lqz = LSE_m s_m - log n ; lw -= lqz
-          const float lse = p.lqz[c][kb] + logf((float)navail);
-#pragma unroll
-          for (int m = 0; m < MAXM; ++m) {
-            // shared dims: responsibilities of the mixture; private dims: the own posterior with weight 1
-            const bool own = (m == c);
-            if (m < M && avail[m] && (l < Ls || own)) {
-              const float r = (l < Ls) ? expf(p.lq_all[c][(long long)m * K * B + kb] - lse) : 1.0f;
-              const float dz_q = lat_dlogp_dz(family, z, mu[m], sd[m]);
-              gz -= g * r * dz_q;
-              if (!dreg) {  // IWAE differentiates the q parameters directly as well
-                dmu[m] += -g * r * (-dz_q);
-                dsd[m] += -g * r * lat_dlogp_dsd(family, z, mu[m], sd[m]);
-              }
-            }
-          }
-          float gtot = gz + p.dz_dec[c][zo];
-          if (dreg) gtot *= wk;  // gradient hook on z (mmvae_model.py:263-266)
-          const float t = lat_t(family, p.noise[c][zo]);
-          // static accumulation into the conditioning modality's slot
-#pragma unroll
-          for (int m = 0; m < MAXM; ++m) {
-            if (m == c) {
-              dmu[m] += gtot;
-              dsd[m] += gtot * t;
-            }
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < MAXM; ++m) {
-      if (m < M) {
-        p.dmu[m][o] = dmu[m];
-        p.dsd[m][o] = dsd[m];
-      }
-    }
-    if (dprior_sd) dprior_sd[o] = dps;  // per-row term [B, L]: the caller sums the rows in a fixed order
+    lat_bwd_dim(p, M, K, B, L, Ls, beta, family, dreg, gs, inv_n, navail, avail, b, l,
+                [&](int, long long, float g, float z) {
+                  dps += g * lat_dlogp_dsd(family, z, pm, ps);
+                  return g * lat_dlogp_dz(family, z, pm, ps);
+                });
+    if (dprior_sd) dprior_sd[(long long)b * L + l] = dps;  // per-row term [B, L]: the caller sums the rows in a fixed order
   }
 }
 
@@ -498,24 +358,15 @@ int mvk_mmvae_latent_fwd(const float* const* mu, const float* const* sd, const f
                          const uint8_t* const* masks, const float* prior_mean, const float* prior_sd, int M, int K,
                          int B, int L, int family, float* const* z, float* const* lpz, float* const* lqz,
                          float* const* lq_all, int shared_dims, float* const* lqw, void* stream) {
-  if (!mu || !sd || !noise || !prior_mean || !prior_sd || !z || !lpz || !lqz || !lq_all || M < 1 || M > MAXM ||
-      K < 1 || L < 1 || family < 0 || family > 1 || shared_dims < 1 || shared_dims > L || (shared_dims < L && !lqw))
+  if (!prior_mean || !prior_sd || L < 1 || shared_dims < 1 || shared_dims > L || (shared_dims < L && !lqw)) return MVK_EINVAL;
+  const int rc = lat_check(mu && sd && noise && z && lpz && lqz && lq_all, M, K, B, family);
+  if (rc != LAT_LAUNCH) return rc;
+  LatFwdPtrs p{};
+  if (!lat_fill(p.mu, mu, M) || !lat_fill(p.sd, sd, M) || !lat_fill(p.noise, noise, M) || !lat_fill(p.z, z, M) ||
+      !lat_fill(p.lpz, lpz, M) || !lat_fill(p.lqz, lqz, M) || !lat_fill(p.lq_all, lq_all, M))
     return MVK_EINVAL;
-  if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
-  if ((long long)M * K * B > 0x7fffffffLL) return MVK_EINVAL;  // row indices are int: M*K*B < 2^31 (include/mvk.h)
-  MmPtrs p{};
-  for (int m = 0; m < M; ++m) {
-    if (!mu[m] || !sd[m] || !noise[m] || !z[m] || !lpz[m] || !lqz[m] || !lq_all[m]) return MVK_EINVAL;
-    p.mu[m] = mu[m];
-    p.sd[m] = sd[m];
-    p.noise[m] = noise[m];
-    p.mask[m] = masks ? masks[m] : nullptr;
-    p.z[m] = z[m];
-    p.lpz[m] = lpz[m];
-    p.lqz[m] = lqz[m];
-    p.lq_all[m] = lq_all[m];
-    p.lqw[m] = lqw ? lqw[m] : nullptr;
-  }
+  lat_fill(p.mask, masks, M, false);
+  lat_fill(p.lqw, lqw, M, false);
   long long rows = (long long)M * K * B;
   hipLaunchKernelGGL(latent_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, mvk_stream(stream), p,
                      prior_mean, prior_sd, M, K, B, L, shared_dims, family);
@@ -556,27 +407,15 @@ int mvk_mmvae_latent_bwd(const float* const* mu, const float* const* sd, const f
                          const float* const* lqz, const float* const* dz_dec, int M, int K, int B, int L, int family,
                          int dreg, const float* gscale, float* const* dmu, float* const* dsd, float* dprior_sd,
                          int shared_dims, float beta, void* stream) {
-  if (!mu || !sd || !noise || !z || !prior_mean || !prior_sd || !w || !lq_all || !lqz || !dz_dec || !dmu || !dsd ||
-      M < 1 || M > MAXM || K < 1 || L < 1 || family < 0 || family > 1 || shared_dims < 1 || shared_dims > L)
+  if (!prior_mean || !prior_sd || L < 1 || shared_dims < 1 || shared_dims > L) return MVK_EINVAL;
+  const int rc = lat_check(mu && sd && noise && z && w && lq_all && lqz && dz_dec && dmu && dsd, M, K, B, family);
+  if (rc != LAT_LAUNCH) return rc;
+  LatBwdPtrs p{};
+  if (!lat_fill(p.mu, mu, M) || !lat_fill(p.sd, sd, M) || !lat_fill(p.noise, noise, M) || !lat_fill(p.z, z, M) ||
+      !lat_fill(p.w, w, M) || !lat_fill(p.lq_all, lq_all, M) || !lat_fill(p.lqz, lqz, M) ||
+      !lat_fill(p.dz_dec, dz_dec, M) || !lat_fill(p.dmu, dmu, M) || !lat_fill(p.dsd, dsd, M))
     return MVK_EINVAL;
-  if (B <= 0) return B == 0 ? MVK_OK : MVK_EINVAL;
-  if ((long long)M * K * B > 0x7fffffffLL) return MVK_EINVAL;  // row indices are int: M*K*B < 2^31 (include/mvk.h)
-  BwdPtrs p{};
-  for (int m = 0; m < M; ++m) {
-    if (!mu[m] || !sd[m] || !noise[m] || !z[m] || !w[m] || !lq_all[m] || !lqz[m] || !dz_dec[m] || !dmu[m] || !dsd[m])
-      return MVK_EINVAL;
-    p.mu[m] = mu[m];
-    p.sd[m] = sd[m];
-    p.noise[m] = noise[m];
-    p.z[m] = z[m];
-    p.mask[m] = masks ? masks[m] : nullptr;
-    p.w[m] = w[m];
-    p.lq_all[m] = lq_all[m];
-    p.lqz[m] = lqz[m];
-    p.dz_dec[m] = dz_dec[m];
-    p.dmu[m] = dmu[m];
-    p.dsd[m] = dsd[m];
-  }
+  lat_fill(p.mask, masks, M, false);
   hipStream_t s = mvk_stream(stream);
   hipLaunchKernelGGL(latent_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, s, p, prior_mean, prior_sd, M, K, B, L,
                      shared_dims, beta, family, dreg, gscale, dprior_sd);

@@ -2592,6 +2592,35 @@ class MMVAEState:
         self.resp = None         # CMVAE: q(cluster | u_c) rows [K,B,C]
 
 
+# ---- shared by the two latent nodes (MMVAELatentFn, CMVAELatentFn) ----
+def _latent_alloc(state, M, K, B, D, like, private):
+    """The outputs of a latent forward launch into `state` (lqw only with private dims) -> the samples z_c [K,B,D]."""
+    state.z = [_new((K, B, D), like) for _ in range(M)]
+    state.lpz = [_new((K, B), like) for _ in range(M)]
+    state.lqz = [_new((K, B), like) for _ in range(M)]
+    state.lq_all = [_new((M, K, B), like) for _ in range(M)]
+    state.lqw = [_new((K, B), like) for _ in range(M)] if private else None
+    return state.z
+
+
+def _mask_array(masks):
+    return ptr_array(masks) if masks is not None else None
+
+
+def _dz_or_zeros(dzs, zs):
+    """The decoders' gradients of the samples, zeros where a sample reached no decoder."""
+    return [(_c(d) if d is not None else torch.zeros_like(zs[i])) for i, d in enumerate(dzs)]
+
+
+def _sum_rows(rows):
+    """Per-batch-row terms [B, n] of a parameter gradient -> their sum [n], in a fixed order."""
+    B, n = rows.shape
+    out = _zeros((n,), rows)
+    ws = _ws(rows)
+    call("mvk_colsum_acc", ptr(rows), None, NONE, ptr(out), B, n, ptr(ws), ws.numel(), stream_ptr())
+    return out
+
+
 class MMVAELatentFn(Function):
     """(mu_c, std_c)_c, prior_std -> z_c [K,B,L] for every conditioning modality; also fills state.lpz / lqz."""
 
@@ -2603,17 +2632,11 @@ class MMVAELatentFn(Function):
         prior_std = _c(prior_std.reshape(-1))
         prior_mean = _c(prior_mean.reshape(-1))
         K, B, L = noises[0].shape
-        zs = [_new((K, B, L), mus[0]) for _ in range(M)]
-        state.lpz = [_new((K, B), mus[0]) for _ in range(M)]
-        state.lqz = [_new((K, B), mus[0]) for _ in range(M)]
-        state.lq_all = [_new((M, K, B), mus[0]) for _ in range(M)]
         Ls = L if state.shared_dims is None else int(state.shared_dims)
-        state.lqw = [_new((K, B), mus[0]) for _ in range(M)] if Ls < L else None
-        marr = ptr_array(masks) if masks is not None else None
-        call("mvk_mmvae_latent_fwd", ptr_array(mus), ptr_array(sds), ptr_array(noises), marr, ptr(prior_mean),
+        zs = _latent_alloc(state, M, K, B, L, mus[0], private=Ls < L)
+        call("mvk_mmvae_latent_fwd", ptr_array(mus), ptr_array(sds), ptr_array(noises), _mask_array(masks), ptr(prior_mean),
              ptr(prior_std), M, K, B, L, family, ptr_array(zs), ptr_array(state.lpz), ptr_array(state.lqz),
              ptr_array(state.lq_all), Ls, ptr_array(state.lqw) if state.lqw is not None else None, stream_ptr())
-        state.z = zs
         ctx.save_for_backward(prior_mean, prior_std, *mus, *sds)
         ctx.state, ctx.noises, ctx.masks = state, noises, masks
         ctx.family, ctx.dreg, ctx.M = family, dreg, M
@@ -2628,19 +2651,15 @@ class MMVAELatentFn(Function):
         mus, sds = saved[2 : 2 + M], saved[2 + M :]
         st = ctx.state
         K, B, L = ctx.noises[0].shape
-        dzs = [(_c(d) if d is not None else torch.zeros_like(st.z[i])) for i, d in enumerate(dzs)]
+        dzs = _dz_or_zeros(dzs, st.z)
         dmus = [_new((B, L), mus[0]) for _ in range(M)]
         dsds = [_new((B, L), mus[0]) for _ in range(M)]
-        dprior_rows = _new((B, L), mus[0])  # per-row terms of d loss / d prior_std, summed below in a fixed order
-        marr = ptr_array(ctx.masks) if ctx.masks is not None else None
-        call("mvk_mmvae_latent_bwd", ptr_array(mus), ptr_array(sds), ptr_array(ctx.noises), ptr_array(st.z), marr,
-             ptr(prior_mean), ptr(prior_std), ptr_array(st.w), ptr_array(st.lq_all), ptr_array(st.lqz),
+        dprior_rows = _new((B, L), mus[0])  # per-row terms of d loss / d prior_std
+        call("mvk_mmvae_latent_bwd", ptr_array(mus), ptr_array(sds), ptr_array(ctx.noises), ptr_array(st.z),
+             _mask_array(ctx.masks), ptr(prior_mean), ptr(prior_std), ptr_array(st.w), ptr_array(st.lq_all), ptr_array(st.lqz),
              ptr_array(dzs), M, K, B, L, ctx.family, ctx.dreg, ptr(st.gloss), ptr_array(dmus), ptr_array(dsds),
              ptr(dprior_rows), L if st.shared_dims is None else int(st.shared_dims), float(st.beta), stream_ptr())
-        dprior = _zeros((L,), mus[0])
-        ws = _ws(dprior_rows)
-        call("mvk_colsum_acc", ptr(dprior_rows), None, NONE, ptr(dprior), B, L, ptr(ws), ws.numel(), stream_ptr())
-        return (None, None, None, None, None, None, dprior.view(1, L), *dmus, *dsds)
+        return (None, None, None, None, None, None, _sum_rows(dprior_rows).view(1, L), *dmus, *dsds)
 
 
 class MMVAEPlusCrossLatentFn(Function):
@@ -2758,17 +2777,11 @@ class CMVAELatentFn(Function):
         K, B, D = noises[0].shape
         C, Ls = cmean.shape
         assert Ls == int(state.shared_dims) and wsd.numel() == D - Ls and csd.shape == cmean.shape and clogit.numel() == C
-        zs = [_new((K, B, D), mus[0]) for _ in range(M)]
-        state.lpz = [_new((K, B), mus[0]) for _ in range(M)]
-        state.lqz = [_new((K, B), mus[0]) for _ in range(M)]
-        state.lq_all = [_new((M, K, B), mus[0]) for _ in range(M)]
-        state.lqw = [_new((K, B), mus[0]) for _ in range(M)]
+        zs = _latent_alloc(state, M, K, B, D, mus[0], private=True)
         state.resp = [_new((K, B, C), mus[0]) for _ in range(M)]
-        marr = ptr_array(masks) if masks is not None else None
-        call("mvk_cmvae_latent_fwd", ptr_array(mus), ptr_array(sds), ptr_array(noises), marr, ptr(cmean), ptr(csd), ptr(clogit),
-             ptr(wsd), M, K, B, D, family, C, ptr_array(zs), ptr_array(state.lpz), ptr_array(state.lqz),
+        call("mvk_cmvae_latent_fwd", ptr_array(mus), ptr_array(sds), ptr_array(noises), _mask_array(masks), ptr(cmean), ptr(csd),
+             ptr(clogit), ptr(wsd), M, K, B, D, family, C, ptr_array(zs), ptr_array(state.lpz), ptr_array(state.lqz),
              ptr_array(state.lq_all), Ls, ptr_array(state.lqw), ptr_array(state.resp), stream_ptr())
-        state.z = zs
         ctx.save_for_backward(cmean, csd, clogit, wsd, *mus, *sds)
         ctx.state, ctx.noises, ctx.masks = state, noises, masks
         ctx.family, ctx.dreg, ctx.M = family, dreg, M
@@ -2785,19 +2798,15 @@ class CMVAELatentFn(Function):
         st = ctx.state
         K, B, D = ctx.noises[0].shape
         C, Ls = cmean.shape
-        dzs = [(_c(d) if d is not None else torch.zeros_like(st.z[i])) for i, d in enumerate(dzs)]
+        dzs = _dz_or_zeros(dzs, st.z)
         dmus = [_new((B, D), mus[0]) for _ in range(M)]
         dsds = [_new((B, D), mus[0]) for _ in range(M)]
-        n = C * Ls + C
-        rows = _new((B, n), mus[0])  # per-row terms of d loss / d (means, logits), summed below in a fixed order
-        marr = ptr_array(ctx.masks) if ctx.masks is not None else None
-        call("mvk_cmvae_latent_bwd", ptr_array(mus), ptr_array(sds), ptr_array(ctx.noises), ptr_array(st.z), marr, ptr(cmean),
-             ptr(csd), ptr(clogit), ptr(wsd), ptr_array(st.w), ptr_array(st.lq_all), ptr_array(st.lqz), ptr_array(st.resp),
-             ptr_array(dzs), M, K, B, D, ctx.family, ctx.dreg, C, ptr(st.gloss), ptr_array(dmus), ptr_array(dsds), ptr(rows),
-             Ls, float(st.beta), stream_ptr())
-        dparams = _zeros((n,), mus[0])
-        ws = _ws(rows)
-        call("mvk_colsum_acc", ptr(rows), None, NONE, ptr(dparams), B, n, ptr(ws), ws.numel(), stream_ptr())
+        rows = _new((B, C * Ls + C), mus[0])  # per-row terms of d loss / d (means, logits)
+        call("mvk_cmvae_latent_bwd", ptr_array(mus), ptr_array(sds), ptr_array(ctx.noises), ptr_array(st.z),
+             _mask_array(ctx.masks), ptr(cmean), ptr(csd), ptr(clogit), ptr(wsd), ptr_array(st.w), ptr_array(st.lq_all),
+             ptr_array(st.lqz), ptr_array(st.resp), ptr_array(dzs), M, K, B, D, ctx.family, ctx.dreg, C, ptr(st.gloss),
+             ptr_array(dmus), ptr_array(dsds), ptr(rows), Ls, float(st.beta), stream_ptr())
+        dparams = _sum_rows(rows)
         return (None, None, None, None, None, None, None, dparams[: C * Ls].view(C, Ls), dparams[C * Ls :].view(ctx.logit_shape),
                 *dmus, *dsds)
 

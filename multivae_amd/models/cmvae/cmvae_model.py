@@ -5,7 +5,8 @@ predict_clusters :546-619, prune_clusters :621-711, compute_joint_nll :732-788.
 
 The model is MMVAE+ (shared latent u, private latents w_m handled as ONE concatenated latent [u, w]) whose prior of u is a
 learnable mixture over `number_of_clusters` clusters and whose prior of w is fixed; the latent stage runs on csrc/cmvae.hip,
-everything else (cross-modal private draws, reconstruction NLL, IWAE / DReG objective) on the MMVAE+ kernels.
+everything else (cross-modal private draws, reconstruction NLL, IWAE / DReG objective) on the MMVAE+ kernels.  The forward pass
+and compute_joint_nll (all modalities) are SharedPrivateMultiVAE's (models/base/shared_private_model.py, shared with MMVAEPlus).
 
 Deviation from the reference's literal form.  The reference takes an explicit expectation over q(c|u) = softmax_c(a_c) + 1e-20,
 a_c = log pi_c + log p(u|c): lw = sum_c q_c (lpx + beta (a_c + log p(w) - log q(u|X) - log q(w|x) - log q_c)).  Up to the 1e-20
@@ -13,17 +14,14 @@ a_c = log pi_c + log p(u|c): lw = sum_c q_c (lpx + beta (a_c + log p(w) - log q(
 kernel evaluates.  With a pruned cluster (a logit of -inf) the literal form is 1e-20 * (-inf) = -inf for every sample; here
 the cluster is simply absent (zero responsibility, no gradient), so a pruned model can still be evaluated and trained.
 predict_clusters' norm_lliks is likewise logsumexp_c(.) / latent_dim: finite where a p(c|z) underflows to 0 (literal: 0 * inf)."""
-import math
-
 import torch
 from torch import nn
 from torch.utils.data import DataLoader
 
-from ... import _lib, kernels, schedule
-from ...data.utils import drop_unused_modalities, set_inputs_to_device
-from ..base import BaseMultiVAE
+from ... import _lib, kernels
+from ...data.utils import set_inputs_to_device
+from ..base import SharedPrivateMultiVAE
 from ..base.base_utils import ModelOutput
-from ..nn.default_architectures import BaseDictDecodersMultiLatents, BaseDictEncoders_MultiLatents
 from .cmvae_config import CMVAEConfig
 
 
@@ -35,17 +33,11 @@ def prune_entropy(pc_z):
     return h / torch.log(torch.count_nonzero(pc_z, dim=0).to(h.dtype))
 
 
-class CMVAE(BaseMultiVAE):
+class CMVAE(SharedPrivateMultiVAE):
     def __init__(self, model_config: CMVAEConfig, encoders: dict = None, decoders: dict = None):
-        if model_config.modalities_specific_dim is None:
-            raise AttributeError("The modalities_specific_dim attribute must be provided in the model config.")
         super().__init__(model_config, encoders, decoders)
-        if model_config.prior_and_posterior_dist not in ("laplace_with_softmax", "normal", "normal_with_softplus"):
-            raise AttributeError(" The posterior_dist parameter must be  either 'laplace_with_softmax','normal' or "
-                                 f"'normal_with_softplus'.  {model_config.prior_and_posterior_dist} was provided.")
         S, L = model_config.modalities_specific_dim, model_config.latent_dim
         self.model_name = "CMVAE"
-        self.multiple_latent_spaces = True
         self.n_clusters = int(model_config.number_of_clusters)
         if not 1 <= self.n_clusters <= _lib.CMVAE_MAX_CLUSTERS:
             raise AttributeError(f"number_of_clusters must be in 1 .. {_lib.CMVAE_MAX_CLUSTERS}, got {self.n_clusters}")
@@ -54,11 +46,6 @@ class CMVAE(BaseMultiVAE):
             raise AttributeError(f"number_of_clusters = {self.n_clusters} with latent_dim = {L} needs a cluster table of {table} "
                                  f"floats; the CMVAE latent kernel holds at most {_lib.CMVAE_MAX_LDS_FLOATS} (include/mvk.h): "
                                  "use fewer clusters or a smaller latent_dim")
-        self.beta = model_config.beta
-        self.modalities_specific_dim = S
-        self.reconstruction_option = model_config.reconstruction_option
-        self.style_dims = {m: S for m in self.encoders}
-        self.objective = model_config.loss
         # priors of the private spaces used for cross-modal reconstruction (mean fixed, scale learnable)
         self.r_mean_priors = nn.ParameterDict()
         self.r_logvars_priors = nn.ParameterDict()
@@ -75,31 +62,10 @@ class CMVAE(BaseMultiVAE):
         self.logvar_clusters = nn.ParameterList([nn.Parameter(torch.zeros(1, L), requires_grad=False)
                                                  for _ in range(self.n_clusters)])
 
-    def default_encoders(self, model_config) -> nn.ModuleDict:
-        return BaseDictEncoders_MultiLatents(input_dims=model_config.input_dims, latent_dim=model_config.latent_dim,
-                                             modality_dims={m: model_config.modalities_specific_dim
-                                                            for m in model_config.input_dims})
-
-    def default_decoders(self, model_config) -> nn.ModuleDict:
-        return BaseDictDecodersMultiLatents(input_dims=model_config.input_dims, latent_dim=model_config.latent_dim,
-                                            modality_dims={m: model_config.modalities_specific_dim
-                                                           for m in model_config.input_dims})
-
     @property
     def pc_params(self):
         """Weights of the prior distribution over the clusters."""
         return torch.softmax(self._pc_params, dim=-1)
-
-    @property
-    def _std_family(self):
-        return _lib.FAMILY[self.model_config.prior_and_posterior_dist]
-
-    @property
-    def _family(self):  # density / sampling family of the latent kernels
-        return 1 if self.model_config.prior_and_posterior_dist == "laplace_with_softmax" else 0
-
-    def _log_var_to_std(self, log_var):
-        return kernels.MMVAEStdFn.apply(log_var, self._std_family)
 
     def _cluster_params(self):
         """-> stacked means [C, L], stds [C, L] (no gradient: the log-variances are fixed), logits [C]."""
@@ -107,79 +73,16 @@ class CMVAE(BaseMultiVAE):
         stds = self._log_var_to_std(torch.cat([p.detach() for p in self.logvar_clusters], dim=0))
         return means, stds, self._pc_params
 
-    def forward(self, inputs, **kwargs):
-        """kwargs: K, noise = {cond: {"u": [K,B,L], "w": [K,B,S], other modality: [K,B,S]}} (explicit noise in the
-        reference's draw order), detailed_output."""
-        inputs = drop_unused_modalities(inputs)
-        K = int(kwargs.pop("K", self.model_config.K))
-        noise = kwargs.pop("noise", None)
-        if self.objective not in ("dreg_looser", "iwae_looser"):
-            raise NotImplementedError()
-        dreg = self.objective == "dreg_looser"
-        mods = list(inputs.data.keys())
-        M = len(mods)
-        L, S = self.latent_dim, self.modalities_specific_dim
-        D = L + S
-        family = self._family
-        uniform = family == 1
-
-        def encode_one(m):
-            out = self.encoders[m](inputs.data[m])
-            mu = torch.cat([out.embedding, out.style_embedding], dim=-1)
-            sd = torch.cat([self._log_var_to_std(out.log_covariance),
-                            self._log_var_to_std(out.style_log_covariance)], dim=-1)
-            return mu, sd
-
-        order = self._branch_order(inputs, mods)
-        enc = schedule.run_branches(order, encode_one, inputs.data[order[0]].device)
-        mus = [enc[m][0] for m in mods]
-        sds = [enc[m][1] for m in mods]
-        B = mus[0].shape[0]
-        device = mus[0].device
-        noises, cross_noise = [], {}
-        for c in mods:  # draw order of the reference: u, w, then one private-prior draw per other modality
-            nu = self._noise((K, B, L), device, None if noise is None else noise[c]["u"], uniform=uniform)
-            nw = self._noise((K, B, S), device, None if noise is None else noise[c]["w"], uniform=uniform)
-            noises.append(torch.cat([nu, nw], dim=-1))
-            for r in mods:
-                if r != c:
-                    cross_noise[(c, r)] = self._noise((K, B, S), device, None if noise is None else noise[c][r],
-                                                      uniform=uniform)
-        masks = None
-        if hasattr(inputs, "masks"):
-            masks = [inputs.masks[m].to(torch.bool).contiguous() for m in mods]
-        state = kernels.MMVAEState()
-        state.shared_dims, state.beta = L, float(self.beta)
+    def _latent_node(self, state, noises, masks, family, dreg, mus, sds):
         means, stds, logits = self._cluster_params()
         wstd = self._log_var_to_std(self.w_logvar_prior.detach())
-        zs = kernels.CMVAELatentFn.apply(state, noises, masks, family, int(dreg), wstd, stds, means, logits, *mus, *sds)
-        mod_prior_std = {r: self._log_var_to_std(self.r_logvars_priors[r]) for r in mods}
+        return kernels.CMVAELatentFn.apply(state, noises, masks, family, dreg, wstd, stds, means, logits, *mus, *sds)
 
-        def decode_all(r):  # every conditioning modality's latent through decoder r: ONE pass over the M * K * B stacked rows
-            zins = []
-            for ci, c in enumerate(mods):
-                if r == c:
-                    zin = zs[ci]
-                else:
-                    zin = kernels.MMVAEPlusCrossLatentFn.apply(zs[ci], mod_prior_std[r], cross_noise[(c, r)], L, family)
-                zins.append(zin.reshape(-1, D))
-            # as in MMVAEPlus.forward: decoders that declare their rows independent take the stacked rows in one pass, a
-            # user-written decoder is run pair by pair like in the reference (:177-209)
-            if not getattr(self.decoders[r], "rows_independent", False):
-                return [self.decoders[r](zin).reconstruction for zin in zins]
-            rec = self.decoders[r](torch.cat(zins, dim=0)).reconstruction
-            return list(rec.reshape(M, K * B, *rec.shape[1:]).unbind(0))
+    def _cross_prior_logvar(self, r):
+        return self.r_logvars_priors[r]
 
-        dec = schedule.run_branches(self._branch_order(inputs, mods), decode_all, device)
-        recons = [dec[r][c] for c in range(M) for r in mods]
-        spec = self._recon_spec(mods, inputs.data, inputs.masks if masks is not None else None, K, B)
-        loss = kernels.MMVAEObjectiveFn.apply(state, spec, M, dreg, *recons)
-        out = ModelOutput(loss=loss, loss_sum=loss, metrics={})
-        if kwargs.pop("detailed_output", False):
-            out["zss"] = {m: zs[i] for i, m in enumerate(mods)}
-            out["lws"] = {m: state.lw[i] for i, m in enumerate(mods)}
-            out["qcs"] = {m: state.resp[i] for i, m in enumerate(mods)}
-        return out
+    def _detailed_extras(self, state, mods):
+        return {"qcs": {m: state.resp[i] for i, m in enumerate(mods)}}
 
     def _sample(self, mu, sd, shape=()):
         if self._family == 1:
@@ -311,39 +214,3 @@ class CMVAE(BaseMultiVAE):
                 self.n_clusters = int(computed[int(torch.argmin(hs))])
                 self._pc_params.data.copy_(saved[self.n_clusters])
         return h_values
-
-    def compute_joint_nll(self, inputs, K: int = 1000, batch_size_K: int = 100, **kwargs):
-        """-sum_b ln p(x_b) from the pooled importance weights of the forward pass (:732-788): K // n_modalities samples per
-        conditioning modality, all modalities, rescale factors and beta forced to 1 (and restored), and
-        ln p(x_b) ~= logsumexp over all conditioning modalities and samples - ln(count).  kwargs: noise as in forward() with
-        K -> K // n_modalities."""
-        self.eval()
-        if hasattr(inputs, "masks"):
-            raise AttributeError(self._NLL_INCOMPLETE)
-        from ...data.datasets.base import DatasetOutput
-
-        mods = list(inputs.data.keys())
-        k = int(K) // self.n_modalities
-        noise = kwargs.get("noise")
-        B = inputs.data[mods[0]].shape[0]
-        device = inputs.data[mods[0]].device
-        ll = torch.empty(B, dtype=torch.float32, device=device)
-        step = max(1, kernels.IWAE_ROWS_BUDGET // max(k, 1))
-        rescale, beta = self.rescale_factors, self.beta
-        self.rescale_factors, self.beta = {m: 1.0 for m in rescale}, 1.0
-        try:
-            with torch.no_grad():
-                for b0 in range(0, B, step):
-                    b1 = min(B, b0 + step)
-                    part = DatasetOutput(data={m: inputs.data[m][b0:b1] for m in mods})
-                    nz = None
-                    if noise is not None:
-                        nz = {c: {key: v[:, b0:b1] for key, v in noise[c].items()} for c in mods}
-                    out = self.forward(part, K=k, noise=nz, detailed_output=True)
-                    kernels.iwae_reduce([out["lws"][m] for m in mods], out=ll[b0:b1])
-        finally:
-            self.rescale_factors, self.beta = rescale, beta
-        # the latent kernel normalises the mixture of experts by the number of modalities it was given; the reference by
-        # n_modalities (:262): a constant shift of every log-weight
-        shift = math.log(self.n_modalities) - math.log(len(mods))
-        return -(ll.sum() + B * shift)
